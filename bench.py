@@ -8,7 +8,10 @@ pxg_agg_consume (filter + map + group-key hash + staging) -> [N>1: export partia
 RCCL all-to-all by key hash, import] -> pxg_agg_finalize (group sort, count/mean reductions,
 t-digest quantiles, key extraction) — finalized result columns on device.
 
-Legs after the timed region (none of them is inside it):
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line.
+Legs after the timed region (none of them is inside it), run only with --full:
+  * kernel_ms_per_step / kernel_launches_per_step: untimed, fully event-bracketed passes of the
+    step (before the timed region).
   * engine_query: the unmodified binary C2 plan through the C++ engine (pxc_execute_plan).
   * cpu_baseline + parity (rank 0, N=1): the CPU Carnot restatement (oracle/) runs the C2 plan
     over the SAME rows (regenerated on the host, bit-identical to the device generator) as
@@ -32,6 +35,7 @@ sys.path.insert(0, REPO)
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak (MI355X_MICROARCH.md, chip-level parameters)
 SEED = 20250117
 N_PAIR_KEYS = 10_000_000
+DUMP_MAX_BYTES = 48 << 20   # --dump-outputs writes at most this much
 KERNELS = ["agg_consume", "agg_consume_prefix", "agg_records", "agg_publish_sizes", "agg_publish_write", "finalize_init", "slot_flags", "slot_gslot", "group_heads",
            "radix_hist_rank", "radix_hist", "radix_scan", "radix_scatter",
            "run_heads", "group_starts", "group_chunk_count", "chunk_reduce", "group_combine", "classify_groups",
@@ -49,6 +53,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (per-kernel breakdown, engine query, filter/map, C3, C5, "
+                         "C1, CPU baselines + parity, the 1B-row n1 leg, live PMC traffic; N>1: breakdown, PMC, parity); the "
+                         "--no-* options below prune them.  Without it the run is setup, warm-up, the timed steps and the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result columns of the last timed step (rows ordered by group key) as DIR/<name>.npy, float64")
     ap.add_argument("--rows-per-gpu", type=int, default=None,
                     help="default: 100M at N=1 (configs[1], C2); 125M per GPU at N>1 (configs[3], C4: 1B rows at N=8)")
     ap.add_argument("--n1-rows", type=int, default=1_000_000_000,
@@ -202,6 +212,10 @@ def main():
     if args.cpu_shard_child:
         cpu_shard_child(*args.cpu_shard_child)
         return
+    if not args.full:
+        # A plain run measures the headline figure only: every other leg is off.
+        args.no_cpu_baseline = args.no_engine_leg = args.no_pmc = True
+        args.n1_rows = 0
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         # No external launcher: start the N ranks here (fresh interpreters; this process never
@@ -257,8 +271,8 @@ def main():
     ctx.sync()
     # Per-kernel breakdown from one untimed, fully event-bracketed pass (the event records
     # themselves cost time, so the timed region brackets agg_consume only).
-    kernel_ms = profiled_kernels(ctx, step)
-    step_launches = launches_of(ctx, step)
+    kernel_ms = profiled_kernels(ctx, step) if args.full else None
+    step_launches = launches_of(ctx, step) if args.full else None
     ctx.reset_stats()
     ctx.set_profiling(True, only="agg_consume")
     torch.cuda.synchronize()
@@ -280,7 +294,9 @@ def main():
     # bytes of one step are read by the two launches together.
     avg_launch_ms = cons_ms / args.steps
     achieved = alg_bytes / (avg_launch_ms / 1000.0) / 1e9 if launches else None
-    dev_result = agg.result() if not args.no_cpu_baseline else None
+    dev_result = agg.result() if not args.no_cpu_baseline or args.dump_outputs else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dev_result)
     traffic = pmc_traffic(args, n)
 
     # Engine leg (N=1): the unmodified binary C2 plan through pxc_execute_plan over the stored
@@ -407,6 +423,28 @@ def main():
     table.close()
     ctx.close()
     engine.close()
+
+
+def dump_outputs(out_dir, cols):
+    """--dump-outputs: the result columns of the last timed step (service, req_path, count, mean,
+    quantiles), rows ordered by (service, req_path) because the table's group order differs run
+    to run, every array as float64 (exact for the INT64 counts, the STRING offsets and bytes)."""
+    import numpy as np
+    keys = [c.to_list() for c in cols[:2]]
+    order = np.array(sorted(range(len(cols[0])), key=lambda i: (keys[0][i], keys[1][i])), dtype=np.int64)
+    # At most DUMP_MAX_BYTES in all: a larger result keeps a seeded sample of its (ordered) rows.
+    per_row = 8 * (2 + sum(c.values[0].size for c in cols[2:]) + (len(cols[0].data) + len(cols[1].data)) / max(len(order), 1)) if len(order) else 0
+    if per_row * len(order) > DUMP_MAX_BYTES:
+        keep = np.random.default_rng(SEED).choice(len(order), int(DUMP_MAX_BYTES // per_row), replace=False)
+        order = order[np.sort(keep)]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, ks in (("service", keys[0]), ("req_path", keys[1])):
+        raw = [ks[i].encode(errors="surrogateescape") for i in order]
+        lens = np.array([len(b) for b in raw], dtype=np.float64)
+        np.save(os.path.join(out_dir, name + "_offsets.npy"), np.concatenate([[0.0], np.cumsum(lens)]))
+        np.save(os.path.join(out_dir, name + "_bytes.npy"), np.frombuffer(b"".join(raw), dtype=np.uint8).astype(np.float64))
+    for name, c in zip(("count", "mean", "quantiles"), cols[2:]):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(c.values[order], dtype=np.float64))
 
 
 def profiled_kernels(ctx, step):
@@ -636,7 +674,7 @@ def multi_main(args, rank, world, local_rank):
         for _ in range(args.warmup):
             runner.step()
         runner.sync()
-        kernel_ms = runner.profile()
+        kernel_ms = runner.profile() if args.full else None
         runner.start_timing()
         dist.barrier()
         runner.sync()
@@ -665,7 +703,9 @@ def multi_main(args, rank, world, local_rank):
             # rank 0's consume (its shard = rows [0, n), the same consume as the timed one) under
             # two rocprofv3 --pmc passes in a child process; the other ranks wait at the barrier
             pmc = pmc_leg(n)
-        if rank == 0:
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, runner.result())
+        if rank == 0 and args.full:
             sys.path.insert(0, os.path.join(REPO, "tests"))
             try:
                 import parity

@@ -1,7 +1,7 @@
 """bench.py's N > 1 contract on CPU: `bench.py --gpus N` with no external launcher starts its own
 N ranks (gloo rendezvous on 127.0.0.1), runs the barrier-bracketed timed loop, takes the max over
-ranks, gathers the final rows on rank 0 and prints ONE JSON line with n_gpus = N and a parity
-block checked against the generator's ground truth.  The device step is replaced by the CPU
+ranks, gathers the final rows on rank 0 and prints ONE JSON line with n_gpus = N and (--full) a
+parity block checked against the generator's ground truth.  The device step is replaced by the CPU
 stand-in of tests/bench_standin.py (--standin); the device step itself runs in the GPU tests and
 on the driver's node.  A WORLD_SIZE that disagrees with --gpus is refused before anything runs."""
 import json
@@ -20,7 +20,7 @@ def _env():
 
 
 def test_bench_gpus_2_launches_its_own_ranks_and_checks_parity():
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--backend", "gloo", "--standin", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, BENCH, "--full", "--gpus", "2", "--backend", "gloo", "--standin", "--steps", "2", "--warmup", "1",
                         "--rows-per-gpu", "40000"], env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -37,7 +37,7 @@ def test_bench_gpus_2_launches_its_own_ranks_and_checks_parity():
 
 
 def test_bench_three_ranks():
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "3", "--backend", "gloo", "--standin", "--steps", "1", "--warmup", "0",
+    r = subprocess.run([sys.executable, BENCH, "--full", "--gpus", "3", "--backend", "gloo", "--standin", "--steps", "1", "--warmup", "0",
                         "--rows-per-gpu", "20000"], env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
