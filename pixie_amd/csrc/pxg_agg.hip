@@ -1138,9 +1138,10 @@ int32_t Agg::PublishNew(Table* t, uint32_t* n_deferred) {
   PXG_RETURN_IF_ERROR(Launch(ctx, "agg_publish_sizes", AggPublishSizesKernel, dim3(GridFor(cap, 256, 1 << 30)), dim3(256), 0,
                              d_plan.as<const AggPlanDev>(), chunks, slots.as<const unsigned long long>(), cap, sizes));
   PXG_RETURN_IF_ERROR(ScanExclusiveU64(ctx, sizes, sizes, cap, total, sc));
-  uint8_t* pin = static_cast<uint8_t*>(ctx->pinned);
+  const PinnedScratch& pin = *ctx->pinned;
+  static_assert(sizeof(pin.hc_maxlen) == sizeof(hc_maxlen_h), "host mirror and read-back differ");
   {
-    const SmallCopy rb[3] = {{total, 0, 8}, {counters.p, 8, 56}, {hc_maxlen.p, 64, static_cast<uint32_t>(sizeof(hc_maxlen_h))}};
+    const SmallCopy rb[3] = {PXG_PIN_COPY(total, publish_total), PXG_PIN_COPY(counters.p, publish_counters), PXG_PIN_COPY(hc_maxlen.p, hc_maxlen)};
     PXG_RETURN_IF_ERROR(ReadbackSmall(ctx, ctx->stream, rb, hc_active ? 3 : 2));
   }
   uint64_t* rec_p = rec_ok && rec_cap == cap ? prec.as<uint64_t>() : nullptr;
@@ -1159,14 +1160,13 @@ int32_t Agg::PublishNew(Table* t, uint32_t* n_deferred) {
   } else {
     PXG_HIP(hipStreamSynchronize(ctx->stream));
   }
-  uint8_t c[56];
-  uint64_t tot = 0;
-  std::memcpy(&tot, pin, 8);
-  std::memcpy(c, pin + 8, 56);
+  const uint64_t tot = pin.publish_total;
+  uint8_t c[sizeof(pin.publish_counters)];
+  std::memcpy(c, pin.publish_counters, sizeof(c));
   std::memcpy(n_deferred, c + 8, 4);
   std::memcpy(&st_n, c + 16, 8);
   std::memcpy(&hc_n, c + 48, 8);
-  if (hc_active) std::memcpy(hc_maxlen_h, pin + 64, sizeof(hc_maxlen_h));
+  if (hc_active) std::memcpy(hc_maxlen_h, pin.hc_maxlen, sizeof(hc_maxlen_h));
 
   const uint64_t n_new = tot >> kPublishCountShift;
   const uint64_t words = tot & ((uint64_t(1) << kPublishCountShift) - 1);

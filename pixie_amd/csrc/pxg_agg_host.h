@@ -10,6 +10,11 @@ namespace pxg {
 
 struct HcExport;  // pxg_hc.hip
 
+// Selection workspace of one set of big groups (pxg_select.hip; BigSet::sel).
+struct SelWs {
+  DevBuf spl, cnt, list, bstart, tag, cbase, plan, partial;
+};
+
 struct AggResult {
   int64_t n_groups = 0;
   bool ready = false;
@@ -175,12 +180,13 @@ struct Agg {
     // counts (meta), chains, selection workspace
     struct EarlyBig {
       DevBuf big, chunks, ids, egs, meta, chain_starts, chain_nc;
-      DevBuf spl, cnt, list, bstart, tag, cbase, plan, partial;
+      SelWs sel;
     } early;
     DevBuf fb_list, fb_meta;  // the fallback groups of both sets (full sort path)
     DevBuf chain_list, chain_nc, chain_starts;
-    // big groups by selection (pxg_finalize.hip)
-    DevBuf sel_spl, sel_cnt, sel_bstart, sel_tag, sel_cbase, sel_plan, sel_partial, sel_list, sel_bin;
+    // big groups by selection (pxg_finalize.hip): the late set's workspace, both sets' bins
+    SelWs sel;
+    DevBuf sel_bin;
     RadixPassWs rs;
     // high-cardinality finalize
     DevBuf hc_k[2], hc_v[2], hc_starts, hc_kscr, hc_meta;

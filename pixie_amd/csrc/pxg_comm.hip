@@ -211,7 +211,7 @@ static int32_t AlltoallV2(pxg_agg* agg, Comm& C, int64_t* bytes_sent, int64_t* b
   int64_t* d_recv_cnt = d_send_cnt + n;
   uint8_t* d_recv_hdr = reinterpret_cast<uint8_t*>(d_recv_cnt + n);
   uint8_t* d_send_hdr = d_recv_hdr + static_cast<size_t>(n) * hb;
-  uint8_t* pin8 = static_cast<uint8_t*>(ctx->pinned) + Ctx::kPinnedOps;
+  uint8_t* pin8 = ctx->pinned->ops;
   const size_t back = static_cast<size_t>(n) * (16 + hb);
   if (back + 64 > Ctx::kPinnedBytes - Ctx::kPinnedOps) return SetError(PXG_UNIMPLEMENTED, "%d ranks", n);
   // A failed export still takes part in the {bytes, header} exchange, announcing -1 bytes to every
@@ -323,7 +323,7 @@ extern "C" int32_t pxg_agg_alltoall(pxg_agg* agg, pxg_comm* comm, int64_t* bytes
   int64_t* d_send_cnt = C.counts.as<int64_t>();
   int64_t* d_recv_cnt = d_send_cnt + n;
   uint8_t* d_recv_hdr = reinterpret_cast<uint8_t*>(d_recv_cnt + n);
-  uint8_t* pin8 = static_cast<uint8_t*>(ctx->pinned) + Ctx::kPinnedOps;
+  uint8_t* pin8 = ctx->pinned->ops;
   if (static_cast<size_t>(2 * n) * 8 + static_cast<size_t>(n) * hb > Ctx::kPinnedBytes - Ctx::kPinnedOps)
     return SetError(PXG_UNIMPLEMENTED, "%d ranks", n);
   int64_t* pin = reinterpret_cast<int64_t*>(pin8);
@@ -449,7 +449,7 @@ extern "C" int32_t pxg_agg_gather(pxg_agg* agg, pxg_comm* comm, int32_t root, in
   DevBuf* vbuf[kMaxUdas];
   for (int u = 0; u < n_vcols; ++u) vbuf[u] = a.emit_states ? &R.states : &R.uda_out[u];
   // 1. Headers: every rank's {groups, key payload bytes} to the root.
-  int64_t* pin = reinterpret_cast<int64_t*>(static_cast<uint8_t*>(ctx->pinned) + Ctx::kPinnedOps);
+  int64_t* pin = reinterpret_cast<int64_t*>(ctx->pinned->ops);
   if (static_cast<size_t>(n + 1) * kGatherHdr * 8 > Ctx::kPinnedBytes - Ctx::kPinnedOps) return SetError(PXG_UNIMPLEMENTED, "%d ranks", n);
   PXG_RETURN_IF_ERROR(C.counts.Ensure(static_cast<size_t>(n + 1) * kGatherHdr * 8 + 64));
   int64_t* d_hdr = C.counts.as<int64_t>();  // [0] mine, [1 + r] rank r's (root)

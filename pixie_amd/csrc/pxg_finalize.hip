@@ -1241,10 +1241,10 @@ static bool EarlyBigOn() {
 
 struct SideJoinGuard {
   Ctx* ctx;
-  bool side = false, side2 = false;
+  bool on[2] = {false, false};
   ~SideJoinGuard() {
-    if (side) (void)JoinSide(ctx);
-    if (side2) (void)JoinSide2(ctx);
+    for (int i = 0; i < 2; ++i)
+      if (on[i]) (void)JoinSide(ctx, i);
   }
 };
 
@@ -1298,70 +1298,146 @@ int32_t IssueLanes(Agg& a, int u, uint32_t mask, pxg_column_out& o) {
   return CopyD2H(a.ctx, a.ctx->stream, o.data, d_fin, G);
 }
 
-int32_t AggFinalizeTable(Agg* a) {
-  Ctx* ctx = a->ctx;
-  SideJoinGuard guard{ctx};
+// A set of big groups over its buffers and device counters; the host bounds (n_big, n_chunks,
+// big_max) are the caller's to fill in.
+static BigSet MakeBigSet(BigGroup* big, BigChunk* chunks, const uint32_t* d_count, const uint32_t* d_meta, const uint32_t* large_cnt,
+                         const uint32_t* large_list, const uint32_t* chain_starts, const int32_t* chain_nc, SelWs* sel) {
+  return BigSet{big, chunks, d_count, d_meta, large_cnt, large_list, chain_starts, chain_nc, sel};
+}
+
+// Sizes, allocates and enqueues on stream st the device -> host copies of key column k of a
+// finalized table (a.res): the fixed-width values, or the STRING offsets and data_bytes bytes of
+// payload (the exact length, or an upper bound when the length is not on the host yet).
+static int32_t IssueKeyColumn(Agg& a, int k, hipStream_t st, size_t data_bytes, pxg_column_out& o) {
+  const size_t G = static_cast<size_t>(a.res.n_groups);
+  std::memset(&o, 0, sizeof(o));
+  o.type = a.key_types[k];
+  o.length = static_cast<int64_t>(G);
+  if (o.type == PXG_STRING) {
+    o.offsets = static_cast<int32_t*>(ResultAlloc((G + 1) * 4));
+    o.data = static_cast<uint8_t*>(ResultAlloc(data_bytes + 16));
+    o.data_len = static_cast<int64_t>(data_bytes);
+    if (!o.offsets || !o.data) return SetError(PXG_RESOURCE_UNAVAILABLE, "host result allocation failed");
+    if (G == 0) {
+      o.offsets[0] = 0;
+      return PXG_OK;
+    }
+    PXG_RETURN_IF_ERROR(CopyD2H(a.ctx, st, o.offsets, a.res.key_offsets[k].p, (G + 1) * 4));
+    return CopyD2H(a.ctx, st, o.data, a.res.key_data[k].p, data_bytes);
+  }
+  const size_t w = TypeWidth(o.type);
+  o.values = ResultAlloc(std::max<size_t>(G * w, 1));
+  if (!o.values) return SetError(PXG_RESOURCE_UNAVAILABLE, "host result allocation failed");
+  return G > 0 ? CopyD2H(a.ctx, st, o.values, a.res.key_fixed[k].p, G * w) : PXG_OK;
+}
+
+// The table path of a finalize, phase by phase; AggFinalizeTable below is the sequence.  The
+// fields are the values that cross phases.
+struct TableFinalize {
+  Agg* a;
+  Ctx* ctx;
+  AggResult& R;
+  Agg::FinalizeWs& ws;
+  SideJoinGuard guard;
   HostClock clk;
-  AggResult& R = a->res;
-  Agg::FinalizeWs& ws = a->ws;
-  R.Clear();
-  const uint64_t n = a->st_n;
-  if (n == 0) {
-    R.ready = true;
-    return PXG_OK;
-  }
-  if (n >= (uint64_t(1) << 32)) return SetError(PXG_UNIMPLEMENTED, "more than 2^32 staged rows in one aggregation");
-  // Streams the grouping moves: the plan's value streams.  The owner of a merged exchange moves
-  // only the quantile stream (the items; every other output comes from the merged accumulators,
-  // FinalizeMerged) and the items' weights: cv.p[x_qval] and cv.p[n_vals] after the grouping.
-  const bool mq = a->merged && a->x_qval >= 0;
-  const int nvs = a->merged ? (mq ? 2 : 1) : a->n_vals;
-  PXG_RETURN_IF_ERROR(ws.meta.Ensure(96));
-  uint8_t* meta = ws.meta.as<uint8_t>();
-  uint32_t* d_ngroups = reinterpret_cast<uint32_t*>(meta + 8);
-  unsigned int* d_err = reinterpret_cast<unsigned int*>(meta + 16);
-  uint32_t* d_cls = reinterpret_cast<uint32_t*>(meta + 32);
-  PXG_RETURN_IF_ERROR(Launch(ctx, "finalize_init", FinalizeInitKernel, dim3(1), dim3(64), 0, meta, n));
-
-  // 1. Dense group ids: rank of every occupied table slot (slot order).
-  const uint32_t ngroups = static_cast<uint32_t>(a->inserted);
-  R.n_groups = ngroups;
-  if (ngroups == 0) {
-    R.ready = true;
-    return PXG_OK;
-  }
-  bool keys_on_side2 = false;
-  PXG_RETURN_IF_ERROR(ws.scan.Ensure(ScanScratchBytes(static_cast<int64_t>(std::max<uint64_t>(n, a->cap) + 1)) + 64));
-  void* scan_tmp = ws.scan.p;
-  PXG_RETURN_IF_ERROR(ws.rank.Ensure(static_cast<size_t>(a->cap) * 4 + 16));
-  PXG_RETURN_IF_ERROR(ws.gslot.Ensure(static_cast<size_t>(ngroups) * 4));
-  // Fused split (pxg_group.hip): large aggregations whose radix sort needs more than one pass
-  // (PXG_FSPLIT=0 / 1: tests force it off / on).
+  // Prepare
+  uint64_t n = 0;        // staged rows
+  uint32_t ngroups = 0;
+  bool mq = false;       // merged exchange with a quantile stream
+  int nvs = 0;           // value streams the grouping moves
   int gbits = 1;
-  while ((uint64_t(1) << gbits) < static_cast<uint64_t>(ngroups) + 1) ++gbits;
-  const bool fsplit = gbits > kRadixBits && FusedSplitOn(n);
+  bool fsplit = false, keys_issued = false;
+  uint8_t* meta = nullptr;  // ws.meta (FinalizeInitKernel's layout) and its words
+  uint32_t *d_ngroups = nullptr, *d_cls = nullptr;
+  unsigned int *d_err = nullptr, *d_fallback = nullptr;
   uint64_t* d_ftotal = nullptr;
-  if (!fsplit) {
-    PXG_RETURN_IF_ERROR(DenseIdsBySlot(ctx, a->slots.as<const unsigned long long>(), a->cap, ws.rank.as<uint32_t>(), ws.gslot.as<uint32_t>(),
-                                       d_ngroups, scan_tmp));
-  } else {
-    PXG_RETURN_IF_ERROR(DesignateLargeGroups(ctx, a->slots.as<const unsigned long long>(), a->cap, a->st_slot.as<const uint32_t>(), n,
-                                             ngroups, ws.split_cnt, ws.split_flags, ws.rank.as<uint32_t>(), ws.gslot.as<uint32_t>(),
-                                             d_ngroups, scan_tmp, &d_ftotal));
+  void* scan_tmp = nullptr;
+  // Grouping
+  ConstValPtrs cv;  // the grouped value streams
+  const uint32_t* gstart = nullptr;
+  // The early big set (fused split only): the designated groups are final as soon as the split's
+  // scatter has run, so their big ones start the selection path on side stream 2 while the rest
+  // sort runs on the main stream (issued after the rest sort's launches).
+  bool early_on = false;
+  uint32_t early_gr = 0xFFFFFFFFu, early_nd = 0;
+  uint64_t early_rows = 0;
+  const uint32_t* early_dstarts = nullptr;
+  // Reductions
+  UdaOut uo;
+  bool any_q = false, any_red = false;
+  uint32_t* cbase = nullptr;
+  uint64_t max_chunks = 0;
+  // Quantile sets
+  BigSet SE;  // the early set
+  BigSet SL;  // the late set: class 3 of the classification
+  bool big_select = false;
+  uint32_t n_big_groups = 0;  // the late set's groups (host, after the meta readback)
+  // Final read-back
+  unsigned int err = 0;
+  uint32_t g_dev = 0, n_fallback = 0;
+
+  explicit TableFinalize(Agg* agg) : a(agg), ctx(agg->ctx), R(agg->res), ws(agg->ws), guard{agg->ctx} {}
+
+  // Workspace, FinalizeInit and 1. dense group ids: rank of every occupied table slot (slot
+  // order).  Nothing staged or no group: the (empty) result is ready (R.ready).
+  int32_t Prepare() {
+    R.Clear();
+    n = a->st_n;
+    if (n == 0) {
+      R.ready = true;
+      return PXG_OK;
+    }
+    if (n >= (uint64_t(1) << 32)) return SetError(PXG_UNIMPLEMENTED, "more than 2^32 staged rows in one aggregation");
+    // Streams the grouping moves: the plan's value streams.  The owner of a merged exchange moves
+    // only the quantile stream (the items; every other output comes from the merged accumulators,
+    // FinalizeMerged) and the items' weights: cv.p[x_qval] and cv.p[n_vals] after the grouping.
+    mq = a->merged && a->x_qval >= 0;
+    nvs = a->merged ? (mq ? 2 : 1) : a->n_vals;
+    PXG_RETURN_IF_ERROR(ws.meta.Ensure(96));
+    meta = ws.meta.as<uint8_t>();
+    d_ngroups = reinterpret_cast<uint32_t*>(meta + 8);
+    d_err = reinterpret_cast<unsigned int*>(meta + 16);
+    d_fallback = reinterpret_cast<unsigned int*>(meta + 20);
+    d_cls = reinterpret_cast<uint32_t*>(meta + 32);
+    PXG_RETURN_IF_ERROR(Launch(ctx, "finalize_init", FinalizeInitKernel, dim3(1), dim3(64), 0, meta, n));
+
+    ngroups = static_cast<uint32_t>(a->inserted);
+    R.n_groups = ngroups;
+    if (ngroups == 0) {
+      R.ready = true;
+      return PXG_OK;
+    }
+    PXG_RETURN_IF_ERROR(ws.scan.Ensure(ScanScratchBytes(static_cast<int64_t>(std::max<uint64_t>(n, a->cap) + 1)) + 64));
+    scan_tmp = ws.scan.p;
+    PXG_RETURN_IF_ERROR(ws.rank.Ensure(static_cast<size_t>(a->cap) * 4 + 16));
+    PXG_RETURN_IF_ERROR(ws.gslot.Ensure(static_cast<size_t>(ngroups) * 4));
+    // Fused split (pxg_group.hip): large aggregations whose radix sort needs more than one pass
+    // (PXG_FSPLIT=0 / 1: tests force it off / on).
+    while ((uint64_t(1) << gbits) < static_cast<uint64_t>(ngroups) + 1) ++gbits;
+    fsplit = gbits > kRadixBits && FusedSplitOn(n);
+    if (!fsplit) {
+      PXG_RETURN_IF_ERROR(DenseIdsBySlot(ctx, a->slots.as<const unsigned long long>(), a->cap, ws.rank.as<uint32_t>(), ws.gslot.as<uint32_t>(),
+                                         d_ngroups, scan_tmp));
+    } else {
+      PXG_RETURN_IF_ERROR(DesignateLargeGroups(ctx, a->slots.as<const unsigned long long>(), a->cap, a->st_slot.as<const uint32_t>(), n,
+                                               ngroups, ws.split_cnt, ws.split_flags, ws.rank.as<uint32_t>(), ws.gslot.as<uint32_t>(),
+                                               d_ngroups, scan_tmp, &d_ftotal));
+    }
+
+    clk.Mark("finalize: dense ids");
+    // Group keys out of the arena, on side stream 2 while the radix sort runs on the main
+    // stream (ConvertAggHashMapToRowBatch group columns, agg_node.cc:303-349).  String payloads
+    // are sized by the arena (an upper bound), so no count comes back to the host first.  Side
+    // stream 2 forks here; its launches are issued after the sort's (IssueKeys, from Grouping), so
+    // the host reaches the sort (the critical path) sooner.
+    if (a->n_keys > 0) {
+      PXG_RETURN_IF_ERROR(ForkSide(ctx, 1));
+      guard.on[1] = true;
+    }
+    return PXG_OK;
   }
 
-  clk.Mark("finalize: dense ids");
-  // Group keys out of the arena, on side stream 2 while the radix sort runs on the main
-  // stream (ConvertAggHashMapToRowBatch group columns, agg_node.cc:303-349).  String payloads
-  // are sized by the arena (an upper bound), so no count comes back to the host first.  Side
-  // stream 2 forks here; its launches are issued after the sort's, so the host reaches the
-  // sort (the critical path) sooner.
-  if (a->n_keys > 0) {
-    PXG_RETURN_IF_ERROR(ForkSide2(ctx));
-    guard.side2 = true;
-  }
-  auto IssueKeys = [&]() -> int32_t {
-  {
+  int32_t IssueKeys() {
     KeyOutDev ko;
     for (int k = 0; k < kMaxKeys; ++k) {
       ko.fixed[k] = nullptr;
@@ -1380,215 +1456,191 @@ int32_t AggFinalizeTable(Agg* a) {
     }
     if (a->n_keys > 0) {
       PXG_RETURN_IF_ERROR(ws.scan2.Ensure(ScanScratchBytes(static_cast<int64_t>(ngroups) + 1) + 64));
-      PXG_RETURN_IF_ERROR(LaunchOn(ctx, ctx->side2, "key_extract", KeyExtractKernel, dim3(GridFor(ngroups, 256, 1 << 30)), dim3(256), 0,
+      PXG_RETURN_IF_ERROR(LaunchOn(ctx, ctx->side[1], "key_extract", KeyExtractKernel, dim3(GridFor(ngroups, 256, 1 << 30)), dim3(256), 0,
                                    a->d_plan.as<const AggPlanDev>(), static_cast<const uint32_t*>(ws.gslot.as<uint32_t>()), ngroups,
                                    a->slots.as<const unsigned long long>(), a->arena.as<const uint64_t>(), ko));
       for (int k = 0; k < a->n_keys; ++k) {
         if (a->key_types[k] != PXG_STRING) continue;
         uint32_t* off = R.key_offsets[k].as<uint32_t>();
-        PXG_RETURN_IF_ERROR(ScanExclusiveU32On(ctx, ctx->side2, off, off, ngroups, off + ngroups, ws.scan2.p));
-        PXG_RETURN_IF_ERROR(LaunchOn(ctx, ctx->side2, "key_string_copy", KeyStringCopyKernel, dim3(GridFor(ngroups, 256, 1 << 30)),
+        PXG_RETURN_IF_ERROR(ScanExclusiveU32On(ctx, ctx->side[1], off, off, ngroups, off + ngroups, ws.scan2.p));
+        PXG_RETURN_IF_ERROR(LaunchOn(ctx, ctx->side[1], "key_string_copy", KeyStringCopyKernel, dim3(GridFor(ngroups, 256, 1 << 30)),
                                      dim3(256), 0, a->d_plan.as<const AggPlanDev>(), k,
                                      static_cast<const uint32_t*>(ws.gslot.as<uint32_t>()), ngroups,
                                      a->slots.as<const unsigned long long>(), a->arena.as<const uint64_t>(),
                                      static_cast<const uint32_t*>(R.key_offsets[k].as<uint32_t>()), R.key_data[k].as<uint8_t>()));
       }
-      keys_on_side2 = true;
+      keys_issued = true;
       // Early result: the key columns go to pooled pinned host blocks right behind their
       // kernels (STRING payloads copied up to the arena bound; the exact length is set after
-      // the final synchronisation).
+      // the final synchronisation).  A failed host allocation leaves the ordinary result path.
       if (a->early.want && !a->export_x && !a->merged && !a->emit_states) {
-        bool ok = true;
-        for (int k = 0; k < a->n_keys && ok; ++k) {
-          pxg_column_out& o = a->early.cols[k];
-          std::memset(&o, 0, sizeof(o));
-          o.type = a->key_types[k];
-          o.length = ngroups;
-          if (o.type == PXG_STRING) {
-            o.offsets = static_cast<int32_t*>(ResultAlloc((static_cast<size_t>(ngroups) + 1) * 4));
-            o.data = static_cast<uint8_t*>(ResultAlloc(static_cast<size_t>(a->arena_words) * 8 + 16));
-            ok = o.offsets && o.data;
-            if (ok) {
-              PXG_RETURN_IF_ERROR(CopyD2H(ctx, ctx->side2, o.offsets, R.key_offsets[k].p, (static_cast<size_t>(ngroups) + 1) * 4));
-              if (a->arena_words > 0)
-                PXG_RETURN_IF_ERROR(CopyD2H(ctx, ctx->side2, o.data, R.key_data[k].p, static_cast<size_t>(a->arena_words) * 8));
-            }
-          } else {
-            const size_t w = o.type == PXG_BOOLEAN ? 1 : TypeWidth(o.type);
-            o.values = ResultAlloc(std::max<size_t>(static_cast<size_t>(ngroups) * w, 1));
-            ok = o.values != nullptr;
-            if (ok) PXG_RETURN_IF_ERROR(CopyD2H(ctx, ctx->side2, o.values, R.key_fixed[k].p, static_cast<size_t>(ngroups) * w));
-          }
-        }
-        a->early.keys = ok;
+        int32_t rc = PXG_OK;
+        for (int k = 0; k < a->n_keys && rc == PXG_OK; ++k)
+          rc = IssueKeyColumn(*a, k, ctx->side[1], static_cast<size_t>(a->arena_words) * 8, a->early.cols[k]);
+        if (rc != PXG_OK && rc != PXG_RESOURCE_UNAVAILABLE) return rc;
+        a->early.keys = rc == PXG_OK;
       }
     }
-  }
     return PXG_OK;
-  };
-  // 2. Stable LSD radix sort of (dense id, vals...) by dense id (ceil(log2(G + 1) / 8) passes);
-  //    records without a group (deferred slots) get id G and sort last.  The staging itself is
-  //    left as it is (slots), so finalize can run again and export still works.
-  for (int b = 0; b < 2; ++b) {
-    PXG_RETURN_IF_ERROR(ws.skey[b].Ensure(n * 4 + 16));
-    for (int v = 0; v < nvs; ++v) PXG_RETURN_IF_ERROR(ws.sval[b][v].Ensure(n * 8 + 16));
   }
-  PXG_RETURN_IF_ERROR(ws.scan.Ensure(ScanScratchBytes(static_cast<int64_t>(std::max<uint64_t>(n, a->cap) + 1)) + 64));
-  scan_tmp = ws.scan.p;
-  ConstValPtrs vin;
-  uint32_t* kbuf[2];
-  ValPtrs vbuf[2];
-  for (int b = 0; b < 2; ++b) {
-    kbuf[b] = ws.skey[b].as<uint32_t>();
-    for (int v = 0; v < kMaxVals; ++v) vbuf[b].p[v] = v < nvs ? ws.sval[b][v].as<uint64_t>() : nullptr;
-  }
-  for (int v = 0; v < kMaxVals; ++v) vin.p[v] = v < a->n_vals && !a->merged ? a->st_val[v].as<const uint64_t>() : nullptr;
-  if (a->merged) {  // [quantile items,] weights
-    if (mq) vin.p[0] = a->st_val[a->x_qval].as<const uint64_t>();
-    vin.p[mq ? 1 : 0] = a->st_wt.as<const uint64_t>();
-  }
-  const uint32_t* kin = nullptr;
-  PXG_RETURN_IF_ERROR(ws.gstart.Ensure((static_cast<size_t>(ngroups) + 1) * 4));
-  const uint32_t* gstart = ws.gstart.as<const uint32_t>();
-  // The early big set (fused split only): the designated groups are final as soon as the split's
-  // scatter has run, so their big ones start the selection path on side stream 2 while the rest
-  // sort runs on the main stream (issued after the rest sort's launches, below).
-  bool early_on = false;
-  uint32_t early_gr = 0xFFFFFFFFu, early_nd = 0;
-  uint64_t early_rows = 0;
-  const uint32_t* early_dstarts = nullptr;
-  if (fsplit) {
-    // 2''. The fused split: one 9-bit pass (designated groups final, rest records by their low
-    //      digit), then the rest records' remaining pass(es) by the higher digits.  The pass
-    //      count of the rest comes from G (an upper bound of the rest ids), so the buffer the
-    //      rest sort ends in is known before the rest count comes back.
-    const int p2 = (gbits - kRadixBits + kRadixBits - 1) / kRadixBits;
-    const int fin = p2 == 0 ? 1 : (p2 - 1) & 1;
-    const uint32_t* base = nullptr;
-    PXG_RETURN_IF_ERROR(FusedSplitPass(ctx, a->st_slot.as<const uint32_t>(), n, ws.rank.as<const uint32_t>(), a->cap, ngroups,
-                                       static_cast<const uint64_t*>(d_ftotal), vin, nvs, ws.split_hist, ws.split_tot, ws.fs_keys, ws.rs,
-                                       kbuf[1], vbuf[1], vbuf[fin], &base));
-    uint8_t* pin = static_cast<uint8_t*>(ctx->pinned);
-    PXG_RETURN_IF_ERROR(IssueKeys());
-    PXG_HIP(hipEventSynchronize(ctx->ev_split));
-    uint32_t n_rest = 0;
-    uint64_t ft = 0;
-    std::memcpy(&n_rest, pin + 104, 4);
-    std::memcpy(&ft, pin + 112, 8);
-    const uint32_t nd = std::min<uint32_t>(static_cast<uint32_t>(ft >> 32), kFsMaxU);
-    const uint32_t Gr = ngroups - nd;
-    for (int v = 0; v < kMaxVals; ++v) vin.p[v] = vbuf[fin].p[v];
-    bool plan_q = false;
-    for (int u = 0; u < a->n_udas; ++u) plan_q |= a->uda_kind[u] == PXG_UDA_QUANTILES;
-    if (plan_q && nd > 0 && !a->export_x && !a->merged && !EnvFlag("PXG_BIG_SORT") && EarlyBigOn()) {
-      early_on = true;
-      early_gr = Gr;
-      early_nd = nd;
-      early_rows = n - n_rest;
-      early_dstarts = FusedSplitDesignatedStarts(base);
-      PXG_HIP(hipEventRecord(ctx->ev_early, ctx->stream));  // right behind the split's scatter
+
+  // Value buffers, then the grouping (plain sort / fused split) with the keys issued behind the
+  // sort's launches; leaves cv and gstart.
+  int32_t Grouping() {
+    // 2. Stable LSD radix sort of (dense id, vals...) by dense id (ceil(log2(G + 1) / 8) passes);
+    //    records without a group (deferred slots) get id G and sort last.  The staging itself is
+    //    left as it is (slots), so finalize can run again and export still works.
+    for (int b = 0; b < 2; ++b) {
+      PXG_RETURN_IF_ERROR(ws.skey[b].Ensure(n * 4 + 16));
+      for (int v = 0; v < nvs; ++v) PXG_RETURN_IF_ERROR(ws.sval[b][v].Ensure(n * 8 + 16));
     }
-    if (n_rest > 0) {
-      const uint32_t* rkeys = kbuf[1];
-      if (p2 > 0) {
-        ConstValPtrs rin, rout;
-        for (int v = 0; v < kMaxVals; ++v) rin.p[v] = vbuf[1].p[v];
-        PXG_RETURN_IF_ERROR(RadixSortStreams(ctx, kbuf[1], nullptr, 0, Gr, rin, nvs, n_rest, kbuf, vbuf, ws.rs, &rkeys, &rout, kRadixBits,
-                                             p2 * kRadixBits));
+    ConstValPtrs vin;
+    uint32_t* kbuf[2];
+    ValPtrs vbuf[2];
+    for (int b = 0; b < 2; ++b) {
+      kbuf[b] = ws.skey[b].as<uint32_t>();
+      for (int v = 0; v < kMaxVals; ++v) vbuf[b].p[v] = v < nvs ? ws.sval[b][v].as<uint64_t>() : nullptr;
+    }
+    for (int v = 0; v < kMaxVals; ++v) vin.p[v] = v < a->n_vals && !a->merged ? a->st_val[v].as<const uint64_t>() : nullptr;
+    if (a->merged) {  // [quantile items,] weights
+      if (mq) vin.p[0] = a->st_val[a->x_qval].as<const uint64_t>();
+      vin.p[mq ? 1 : 0] = a->st_wt.as<const uint64_t>();
+    }
+    const uint32_t* kin = nullptr;
+    PXG_RETURN_IF_ERROR(ws.gstart.Ensure((static_cast<size_t>(ngroups) + 1) * 4));
+    gstart = ws.gstart.as<const uint32_t>();
+    if (fsplit) {
+      // 2''. The fused split: one 9-bit pass (designated groups final, rest records by their low
+      //      digit), then the rest records' remaining pass(es) by the higher digits.  The pass
+      //      count of the rest comes from G (an upper bound of the rest ids), so the buffer the
+      //      rest sort ends in is known before the rest count comes back.
+      const int p2 = (gbits - kRadixBits + kRadixBits - 1) / kRadixBits;
+      const int fin = p2 == 0 ? 1 : (p2 - 1) & 1;
+      const uint32_t* base = nullptr;
+      PXG_RETURN_IF_ERROR(FusedSplitPass(ctx, a->st_slot.as<const uint32_t>(), n, ws.rank.as<const uint32_t>(), a->cap, ngroups,
+                                         static_cast<const uint64_t*>(d_ftotal), vin, nvs, ws.split_hist, ws.split_tot, ws.fs_keys, ws.rs,
+                                         kbuf[1], vbuf[1], vbuf[fin], &base));
+      PXG_RETURN_IF_ERROR(IssueKeys());
+      PXG_HIP(hipEventSynchronize(ctx->ev_split));
+      const uint32_t n_rest = ctx->pinned->split_n_rest;
+      const uint64_t ft = ctx->pinned->split_ftotal;
+      const uint32_t nd = std::min<uint32_t>(static_cast<uint32_t>(ft >> 32), kFsMaxU);
+      const uint32_t Gr = ngroups - nd;
+      for (int v = 0; v < kMaxVals; ++v) vin.p[v] = vbuf[fin].p[v];
+      bool plan_q = false;
+      for (int u = 0; u < a->n_udas; ++u) plan_q |= a->uda_kind[u] == PXG_UDA_QUANTILES;
+      if (plan_q && nd > 0 && !a->export_x && !a->merged && !EnvFlag("PXG_BIG_SORT") && EarlyBigOn()) {
+        early_on = true;
+        early_gr = Gr;
+        early_nd = nd;
+        early_rows = n - n_rest;
+        early_dstarts = FusedSplitDesignatedStarts(base);
+        PXG_HIP(hipEventRecord(ctx->ev_early, ctx->stream));  // right behind the split's scatter
       }
-      PXG_RETURN_IF_ERROR(GroupStarts(ctx, rkeys, static_cast<uint64_t>(n_rest), Gr, ws.gstart.as<uint32_t>()));
-    }
-    PXG_RETURN_IF_ERROR(FusedSplitGstart(ctx, base, static_cast<const uint64_t*>(d_ftotal), ngroups, ws.gstart.as<uint32_t>()));
-  } else {
-    PXG_RETURN_IF_ERROR(RadixSortStreams(ctx, a->st_slot.as<const uint32_t>(), ws.rank.as<const uint32_t>(), a->cap, ngroups, vin, nvs,
-                                         n, kbuf, vbuf, ws.rs, &kin, &vin));
-    PXG_RETURN_IF_ERROR(IssueKeys());
-    const uint32_t* skeys = kin;  // sorted dense ids; vin = the values in the same order
-    // 3. Group starts (first index of every id).
-    PXG_RETURN_IF_ERROR(GroupStarts(ctx, skeys, n, ngroups, ws.gstart.as<uint32_t>()));
-  }
-  clk.Mark("finalize: grouping issued");
-  if (a->merged) {  // back to stream numbering: the quantile stream at x_qval, the weights at n_vals
-    const ConstValPtrs sorted = vin;
-    for (int v = 0; v < kMaxVals; ++v) vin.p[v] = nullptr;
-    if (mq) vin.p[a->x_qval] = sorted.p[0];
-    vin.p[a->n_vals] = sorted.p[mq ? 1 : 0];
-  }
-  // 3. UDA reductions (chunk partials, then per-group combine).
-  const ConstValPtrs cv = vin;
-  UdaOut uo;
-  for (int u = 0; u < kMaxUdas; ++u) uo.p[u] = nullptr;
-  bool any_q = false, any_red = false;
-  for (int u = 0; u < a->n_udas; ++u) {
-    const bool q = a->uda_kind[u] == PXG_UDA_QUANTILES;
-    any_q |= q;
-    any_red |= !q && a->uda_kind[u] != PXG_UDA_COUNT && !a->merged;  // (merged: from the accumulators)
-    PXG_RETURN_IF_ERROR(R.uda_out[u].Ensure(static_cast<size_t>(ngroups) * (q ? 7 * 8 : 8)));
-    uo.p[u] = R.uda_out[u].as<uint64_t>();
-  }
-  PXG_RETURN_IF_ERROR(ws.cbase.Ensure((static_cast<size_t>(ngroups) + 1) * 4));
-  uint32_t* cbase = ws.cbase.as<uint32_t>();
-  const uint64_t max_chunks = static_cast<uint64_t>(ngroups) + n / kRedChunk + 1;
-  // With quantiles, issued after the boundary chains are forked (they run in their shadow).
-  auto RunReductions = [&]() -> int32_t {
-  if (any_red) {
-    PXG_RETURN_IF_ERROR(Launch(ctx, "group_chunk_count", GroupChunkCountKernel, dim3(GridFor(ngroups, 256, 1 << 30)), dim3(256), 0, gstart,
-                               ngroups, cbase));
-    PXG_RETURN_IF_ERROR(ScanExclusiveU32(ctx, cbase, cbase, ngroups, cbase + ngroups, scan_tmp));
-    clk.Mark("finalize: red chunk scan");
-    PXG_RETURN_IF_ERROR(ws.partial.Ensure(max_chunks * a->n_udas * kPartialRows * 8));
-    PXG_RETURN_IF_ERROR(ws.cgroup.Ensure(max_chunks * 4 + 16));
-    clk.Mark("finalize: red ensure");
-    PXG_RETURN_IF_ERROR(Launch(ctx, "chunk_group", ChunkGroupKernel, dim3(static_cast<unsigned>((max_chunks + 255) / 256)), dim3(256), 0,
-                               static_cast<const uint32_t*>(cbase), ngroups, ws.cgroup.as<uint32_t>(), static_cast<uint32_t>(max_chunks)));
-    if (n < 32 * static_cast<uint64_t>(ngroups)) {  // groups average < 32 rows: a thread per chunk
-      PXG_RETURN_IF_ERROR(Launch(ctx, "chunk_reduce", ChunkReduceThreadKernel, dim3(static_cast<unsigned>((max_chunks + 255) / 256)),
-                                 dim3(256), 0, a->d_plan.as<const AggPlanDev>(), gstart, static_cast<const uint32_t*>(cbase),
-                                 ws.cgroup.as<const uint32_t>(), ngroups, cv, ws.partial.as<uint64_t>(), max_chunks));
+      if (n_rest > 0) {
+        const uint32_t* rkeys = kbuf[1];
+        if (p2 > 0) {
+          ConstValPtrs rin, rout;
+          for (int v = 0; v < kMaxVals; ++v) rin.p[v] = vbuf[1].p[v];
+          PXG_RETURN_IF_ERROR(RadixSortStreams(ctx, kbuf[1], nullptr, 0, Gr, rin, nvs, n_rest, kbuf, vbuf, ws.rs, &rkeys, &rout, kRadixBits,
+                                               p2 * kRadixBits));
+        }
+        PXG_RETURN_IF_ERROR(GroupStarts(ctx, rkeys, static_cast<uint64_t>(n_rest), Gr, ws.gstart.as<uint32_t>()));
+      }
+      PXG_RETURN_IF_ERROR(FusedSplitGstart(ctx, base, static_cast<const uint64_t*>(d_ftotal), ngroups, ws.gstart.as<uint32_t>()));
     } else {
-      PXG_RETURN_IF_ERROR(Launch(ctx, "chunk_reduce", ChunkReduceKernel, dim3(static_cast<unsigned>((max_chunks * 64 + 255) / 256)),
-                                 dim3(256), 0, a->d_plan.as<const AggPlanDev>(), gstart, static_cast<const uint32_t*>(cbase),
-                                 ws.cgroup.as<const uint32_t>(), ngroups, cv, ws.partial.as<uint64_t>(), max_chunks));
+      PXG_RETURN_IF_ERROR(RadixSortStreams(ctx, a->st_slot.as<const uint32_t>(), ws.rank.as<const uint32_t>(), a->cap, ngroups, vin, nvs,
+                                           n, kbuf, vbuf, ws.rs, &kin, &vin));
+      PXG_RETURN_IF_ERROR(IssueKeys());
+      const uint32_t* skeys = kin;  // sorted dense ids; vin = the values in the same order
+      // 3. Group starts (first index of every id).
+      PXG_RETURN_IF_ERROR(GroupStarts(ctx, skeys, n, ngroups, ws.gstart.as<uint32_t>()));
     }
-  }
-  uint8_t* states = nullptr;
-  const AggPlanDev* cplan = a->d_plan.as<const AggPlanDev>();
-  if (a->emit_states && a->state_rec > 0) {
-    PXG_RETURN_IF_ERROR(R.states.Ensure(static_cast<size_t>(ngroups) * a->state_rec + 16));
-    states = R.states.as<uint8_t>();
-  } else if (a->export_x && a->hplan_x.state_rec > 0) {  // exchange export: every group's Serialize() states
-    PXG_RETURN_IF_ERROR(ws.xstates.Ensure(static_cast<size_t>(ngroups) * a->hplan_x.state_rec + 16));
-    states = ws.xstates.as<uint8_t>();
-    cplan = a->d_plan_x.as<const AggPlanDev>();
-  }
-  if (!a->merged)  // (a merged run's outputs come from its accumulators: XFinalizeStatesKernel)
-    PXG_RETURN_IF_ERROR(Launch(ctx, "group_combine", GroupCombineKernel, dim3(GridFor(ngroups, 256, 1 << 30)), dim3(256), 0,
-                               cplan, gstart, static_cast<const uint32_t*>(cbase), ngroups,
-                               ws.partial.as<const uint64_t>(), max_chunks, uo, states));
-  clk.Mark("finalize: red kernels");
-  if (a->early.want && !states && !a->merged && !a->export_x) {  // early result: the combined values
-    bool ok = true;
-    for (int u = 0; u < a->n_udas && ok; ++u) {
-      if (a->uda_kind[u] == PXG_UDA_QUANTILES) continue;  // after the quantile kernels
-      pxg_column_out& o = a->early.cols[a->n_keys + u];
-      std::memset(&o, 0, sizeof(o));
-      o.type = a->uda_out_type[u];
-      o.length = ngroups;
-      if (a->early.skip && a->early.skip[a->n_keys + u]) continue;
-      o.values = ResultAlloc(std::max<size_t>(static_cast<size_t>(ngroups) * 8, 8));
-      ok = o.values != nullptr;
-      if (ok) PXG_RETURN_IF_ERROR(CopyD2H(ctx, ctx->stream, o.values, R.uda_out[u].p, static_cast<size_t>(ngroups) * 8));
+    clk.Mark("finalize: grouping issued");
+    if (a->merged) {  // back to stream numbering: the quantile stream at x_qval, the weights at n_vals
+      const ConstValPtrs sorted = vin;
+      for (int v = 0; v < kMaxVals; ++v) vin.p[v] = nullptr;
+      if (mq) vin.p[a->x_qval] = sorted.p[0];
+      vin.p[a->n_vals] = sorted.p[mq ? 1 : 0];
     }
-    a->early.vals = ok;
+    cv = vin;
+    return PXG_OK;
   }
-  return PXG_OK;
-  };
-  if (!any_q) PXG_RETURN_IF_ERROR(RunReductions());
-  uint32_t n_big_groups = 0;  // the late set's groups (host, after the meta readback)
-  unsigned int* d_fallback = reinterpret_cast<unsigned int*>(meta + 20);
+
+  // 3. UDA reductions (chunk partials, then per-group combine): the outputs and chunk bounds.
+  int32_t ReductionSetup() {
+    for (int u = 0; u < kMaxUdas; ++u) uo.p[u] = nullptr;
+    for (int u = 0; u < a->n_udas; ++u) {
+      const bool q = a->uda_kind[u] == PXG_UDA_QUANTILES;
+      any_q |= q;
+      any_red |= !q && a->uda_kind[u] != PXG_UDA_COUNT && !a->merged;  // (merged: from the accumulators)
+      PXG_RETURN_IF_ERROR(R.uda_out[u].Ensure(static_cast<size_t>(ngroups) * (q ? 7 * 8 : 8)));
+      uo.p[u] = R.uda_out[u].as<uint64_t>();
+    }
+    PXG_RETURN_IF_ERROR(ws.cbase.Ensure((static_cast<size_t>(ngroups) + 1) * 4));
+    cbase = ws.cbase.as<uint32_t>();
+    max_chunks = static_cast<uint64_t>(ngroups) + n / kRedChunk + 1;
+    return PXG_OK;
+  }
+
+  // With quantiles, issued after the boundary chains are forked (they run in their shadow).
+  int32_t RunReductions() {
+    if (any_red) {
+      PXG_RETURN_IF_ERROR(Launch(ctx, "group_chunk_count", GroupChunkCountKernel, dim3(GridFor(ngroups, 256, 1 << 30)), dim3(256), 0, gstart,
+                                 ngroups, cbase));
+      PXG_RETURN_IF_ERROR(ScanExclusiveU32(ctx, cbase, cbase, ngroups, cbase + ngroups, scan_tmp));
+      clk.Mark("finalize: red chunk scan");
+      PXG_RETURN_IF_ERROR(ws.partial.Ensure(max_chunks * a->n_udas * kPartialRows * 8));
+      PXG_RETURN_IF_ERROR(ws.cgroup.Ensure(max_chunks * 4 + 16));
+      clk.Mark("finalize: red ensure");
+      PXG_RETURN_IF_ERROR(Launch(ctx, "chunk_group", ChunkGroupKernel, dim3(static_cast<unsigned>((max_chunks + 255) / 256)), dim3(256), 0,
+                                 static_cast<const uint32_t*>(cbase), ngroups, ws.cgroup.as<uint32_t>(), static_cast<uint32_t>(max_chunks)));
+      if (n < 32 * static_cast<uint64_t>(ngroups)) {  // groups average < 32 rows: a thread per chunk
+        PXG_RETURN_IF_ERROR(Launch(ctx, "chunk_reduce", ChunkReduceThreadKernel, dim3(static_cast<unsigned>((max_chunks + 255) / 256)),
+                                   dim3(256), 0, a->d_plan.as<const AggPlanDev>(), gstart, static_cast<const uint32_t*>(cbase),
+                                   ws.cgroup.as<const uint32_t>(), ngroups, cv, ws.partial.as<uint64_t>(), max_chunks));
+      } else {
+        PXG_RETURN_IF_ERROR(Launch(ctx, "chunk_reduce", ChunkReduceKernel, dim3(static_cast<unsigned>((max_chunks * 64 + 255) / 256)),
+                                   dim3(256), 0, a->d_plan.as<const AggPlanDev>(), gstart, static_cast<const uint32_t*>(cbase),
+                                   ws.cgroup.as<const uint32_t>(), ngroups, cv, ws.partial.as<uint64_t>(), max_chunks));
+      }
+    }
+    uint8_t* states = nullptr;
+    const AggPlanDev* cplan = a->d_plan.as<const AggPlanDev>();
+    if (a->emit_states && a->state_rec > 0) {
+      PXG_RETURN_IF_ERROR(R.states.Ensure(static_cast<size_t>(ngroups) * a->state_rec + 16));
+      states = R.states.as<uint8_t>();
+    } else if (a->export_x && a->hplan_x.state_rec > 0) {  // exchange export: every group's Serialize() states
+      PXG_RETURN_IF_ERROR(ws.xstates.Ensure(static_cast<size_t>(ngroups) * a->hplan_x.state_rec + 16));
+      states = ws.xstates.as<uint8_t>();
+      cplan = a->d_plan_x.as<const AggPlanDev>();
+    }
+    if (!a->merged)  // (a merged run's outputs come from its accumulators: XFinalizeStatesKernel)
+      PXG_RETURN_IF_ERROR(Launch(ctx, "group_combine", GroupCombineKernel, dim3(GridFor(ngroups, 256, 1 << 30)), dim3(256), 0,
+                                 cplan, gstart, static_cast<const uint32_t*>(cbase), ngroups,
+                                 ws.partial.as<const uint64_t>(), max_chunks, uo, states));
+    clk.Mark("finalize: red kernels");
+    if (a->early.want && !states && !a->merged && !a->export_x) {  // early result: the combined values
+      bool ok = true;
+      for (int u = 0; u < a->n_udas && ok; ++u) {
+        if (a->uda_kind[u] == PXG_UDA_QUANTILES) continue;  // after the quantile kernels
+        pxg_column_out& o = a->early.cols[a->n_keys + u];
+        std::memset(&o, 0, sizeof(o));
+        o.type = a->uda_out_type[u];
+        o.length = ngroups;
+        if (a->early.skip && a->early.skip[a->n_keys + u]) continue;
+        o.values = ResultAlloc(std::max<size_t>(static_cast<size_t>(ngroups) * 8, 8));
+        ok = o.values != nullptr;
+        if (ok) PXG_RETURN_IF_ERROR(CopyD2H(ctx, ctx->stream, o.values, R.uda_out[u].p, static_cast<size_t>(ngroups) * 8));
+      }
+      a->early.vals = ok;
+    }
+    return PXG_OK;
+  }
+
   // Full sort path of a set's big groups for quantile UDA u on stream st: chunk sort, merge
   // passes, digests.  Runs after the set's boundary chains (st must be ordered after them).
-  auto BigSortPath = [&](const BigSet& S, hipStream_t st, int u) -> int32_t {
+  int32_t BigSortPath(const BigSet& S, hipStream_t st, int u) {
     const uint64_t* vals = cv.p[a->uda_val[u]];
     const int at = a->uda_arg_type[u];
     PXG_RETURN_IF_ERROR(ws.keysA.Ensure(n * 8));
@@ -1617,9 +1669,10 @@ int32_t AggFinalizeTable(Agg* a) {
     return LaunchOn(ctx, st, "export_centroids", CentroidListKernel, dim3(S.n_big), dim3(kCentListBlock), 0, static_cast<const BigGroup*>(S.big),
                     S.d_count, ws.keysA.as<const uint64_t>(), ws.keysB.as<const uint64_t>(), ws.bstarts.as<uint32_t>(), S.chain_starts,
                     S.chain_nc, ws.xcent.as<uint64_t>(), ws.xcnt.as<int32_t>());
-  };
+  }
+
   // The selection path of a set (pxg_select.hip) for quantile UDA u.
-  auto SelInOf = [&](int u) -> SelIn {
+  SelIn SelInOf(int u) {
     SelIn in;
     in.vals = cv.p[a->uda_val[u]];
     in.arg_type = a->uda_arg_type[u];
@@ -1629,12 +1682,13 @@ int32_t AggFinalizeTable(Agg* a) {
     in.d_fallback = d_fallback;
     in.out = R.uda_out[u].as<double>();
     return in;
-  };
-  auto EnsureSel = [&](const BigSet& S) -> int32_t { return SelEnsure(S, n, ws.keysA, ws.sel_bin); };
-  auto BigSelectFront = [&](const BigSet& S, hipStream_t st, int u) -> int32_t { return SelFront(ctx, st, S, SelInOf(u)); };
-  auto BigSelectBack = [&](const BigSet& S, hipStream_t st, int u) -> int32_t { return SelBack(ctx, st, S, SelInOf(u)); };
-  BigSet SE;  // the early set
-  if (early_on) {
+  }
+  int32_t EnsureSel(const BigSet& S) { return SelEnsure(S, n, ws.keysA, ws.sel_bin); }
+  int32_t BigSelectFront(const BigSet& S, hipStream_t st, int u) { return SelFront(ctx, st, S, SelInOf(u)); }
+  int32_t BigSelectBack(const BigSet& S, hipStream_t st, int u) { return SelBack(ctx, st, S, SelInOf(u)); }
+
+  // The early set on side stream 2 (early_on).
+  int32_t EarlySet() {
     Agg::FinalizeWs::EarlyBig& E = ws.early;
     const uint32_t nd = early_nd;
     const uint64_t chunk_cap = early_rows / kMidMax + nd + 1;
@@ -1647,48 +1701,50 @@ int32_t AggFinalizeTable(Agg* a) {
     PXG_RETURN_IF_ERROR(E.chain_nc.Ensure(static_cast<size_t>(nd) * 4));
     uint32_t* em = E.meta.as<uint32_t>();  // [0] groups, [1] chunks, [2] largest group, [3] large groups
     uint32_t* large_list = reinterpret_cast<uint32_t*>(E.big.as<uint8_t>() + static_cast<size_t>(nd) * sizeof(BigGroup));
-    SE.big = E.big.as<BigGroup>();
-    SE.chunks = E.chunks.as<BigChunk>();
-    SE.d_count = em;
-    SE.d_meta = em + 1;
+    SE = MakeBigSet(E.big.as<BigGroup>(), E.chunks.as<BigChunk>(), em, em + 1, em + 3, large_list, E.chain_starts.as<const uint32_t>(),
+                    E.chain_nc.as<const int32_t>(), &E.sel);
     SE.n_big = nd;
     SE.n_chunks = static_cast<uint32_t>(chunk_cap);
-    SE.chain_starts = E.chain_starts.as<const uint32_t>();
-    SE.chain_nc = E.chain_nc.as<const int32_t>();
-    SE.spl = &E.spl;
-    SE.cnt = &E.cnt;
-    SE.list = &E.list;
-    SE.bstart = &E.bstart;
-    SE.tag = &E.tag;
-    SE.cbase = &E.cbase;
-    SE.plan = &E.plan;
-    SE.partial = &E.partial;
-    SE.large_list = large_list;
-    SE.large_cnt = em + 3;
     PXG_RETURN_IF_ERROR(EnsureSel(SE));
-    PXG_HIP(hipStreamWaitEvent(ctx->side2, ctx->ev_early, 0));
-    guard.side2 = true;
-    PXG_HIP(hipMemsetAsync(em, 0, 16, ctx->side2));
-    PXG_RETURN_IF_ERROR(LaunchOn(ctx, ctx->side2, "quant_early_list", DesignatedBigListKernel, dim3(1), dim3(256), 0, early_dstarts,
+    PXG_HIP(hipStreamWaitEvent(ctx->side[1], ctx->ev_early, 0));
+    guard.on[1] = true;
+    PXG_HIP(hipMemsetAsync(em, 0, 16, ctx->side[1]));
+    PXG_RETURN_IF_ERROR(LaunchOn(ctx, ctx->side[1], "quant_early_list", DesignatedBigListKernel, dim3(1), dim3(256), 0, early_dstarts,
                                  static_cast<const uint64_t*>(d_ftotal), ngroups, kMidClassMax, E.egs.as<uint32_t>(), E.ids.as<uint32_t>(), em));
     const uint32_t* egs_by_id = E.egs.as<const uint32_t>() - early_gr;  // group starts indexed by group id (ids [Gr, G) only)
-    PXG_RETURN_IF_ERROR(LaunchOn(ctx, ctx->side2, "big_setup", BigSetupKernel, dim3(1), dim3(kSetupBlock), 0, E.ids.as<const uint32_t>(),
+    PXG_RETURN_IF_ERROR(LaunchOn(ctx, ctx->side[1], "big_setup", BigSetupKernel, dim3(1), dim3(kSetupBlock), 0, E.ids.as<const uint32_t>(),
                                  static_cast<const uint32_t*>(em), egs_by_id, SE.big, SE.chunks, em + 1, large_list, em + 3));
-    PXG_RETURN_IF_ERROR(LaunchOn(ctx, ctx->side2, "digest_chain", DigestChainKernel, dim3((nd + kChainWaves - 1) / kChainWaves),
+    PXG_RETURN_IF_ERROR(LaunchOn(ctx, ctx->side[1], "digest_chain", DigestChainKernel, dim3((nd + kChainWaves - 1) / kChainWaves),
                                  dim3(64 * kChainWaves), 0, E.ids.as<const uint32_t>(), static_cast<const uint32_t*>(em), 0u,
                                  E.ids.as<const uint32_t>(), static_cast<const uint32_t*>(em), egs_by_id, E.chain_starts.as<uint32_t>(),
                                  E.chain_nc.as<int32_t>()));
     for (int u = 0; u < a->n_udas; ++u) {
       if (a->uda_kind[u] != PXG_UDA_QUANTILES) continue;
-      PXG_RETURN_IF_ERROR(BigSelectFront(SE, ctx->side2, u));
-      PXG_RETURN_IF_ERROR(BigSelectBack(SE, ctx->side2, u));
+      PXG_RETURN_IF_ERROR(BigSelectFront(SE, ctx->side[1], u));
+      PXG_RETURN_IF_ERROR(BigSelectBack(SE, ctx->side[1], u));
     }
     clk.Mark("finalize: early big set issued");
+    return PXG_OK;
   }
-  bool big_select = false;
-  BigSet SL;  // the late set: class 3 of the classification
-  // 4. Quantile digests.
-  if (any_q) {
+
+  // The late set's buffers hold every group of > kMidMax rows; its large-group count (4 words)
+  // and list follow the groups in ws.big.
+  uint64_t BigCap() const { return n / (kMidMax + 1) + 1; }
+  uint32_t* LateLargeCnt() const { return reinterpret_cast<uint32_t*>(ws.big.as<uint8_t>() + BigCap() * sizeof(BigGroup)); }
+
+  // The late set's big work of quantile UDA u on stream lst.
+  int32_t IssueLate(hipStream_t lst, int u) {
+    if (big_select) PXG_RETURN_IF_ERROR(BigSelectFront(SL, lst, u));
+    if (n_big_groups > 0) {
+      PXG_HIP(hipStreamWaitEvent(lst, ctx->ev_chain, 0));
+      PXG_RETURN_IF_ERROR(big_select ? BigSelectBack(SL, lst, u) : BigSortPath(SL, lst, u));
+    }
+    return PXG_OK;
+  }
+
+  // 4. Quantile digests: classification, chains, the reductions in their shadow, the small / tiny
+  // / mid classes and the late set.
+  int32_t Digests() {
     PXG_RETURN_IF_ERROR(ws.lists.Ensure(static_cast<size_t>(ngroups) * kAllClasses * 4));
     // A merged exchange's groups that received centroid lists get their quantiles from the
     // merged digest (FinalizeMerged): no class here, so the selection path never sees their
@@ -1702,10 +1758,10 @@ int32_t AggFinalizeTable(Agg* a) {
     const uint32_t* lists = ws.lists.as<const uint32_t>();
     // Big-group metadata on the device; one readback of the class counts, the big-group chunk
     // total and the largest group (grid sizes and the merge-pass count).
-    const uint64_t big_cap = n / (kMidMax + 1) + 1;  // groups of > kMidMax rows
+    const uint64_t big_cap = BigCap();
     const uint64_t chunk_cap = n / kMidMax + big_cap + 1;
     PXG_RETURN_IF_ERROR(ws.big.Ensure(big_cap * sizeof(BigGroup) + 16 + big_cap * 4));
-    uint32_t* large_cnt = reinterpret_cast<uint32_t*>(ws.big.as<uint8_t>() + big_cap * sizeof(BigGroup));
+    uint32_t* large_cnt = LateLargeCnt();
     uint32_t* large_list = large_cnt + 4;
     PXG_RETURN_IF_ERROR(ws.bchunks.Ensure(chunk_cap * sizeof(BigChunk)));
     uint32_t* d_bigmeta = reinterpret_cast<uint32_t*>(meta + 48);
@@ -1715,9 +1771,8 @@ int32_t AggFinalizeTable(Agg* a) {
     // Class counts + big-group metadata to pinned memory right away; the host waits on this
     // event only, while the digests below keep the GPU busy.
     clk.Mark("finalize: classes issued");
-    uint8_t* pin = static_cast<uint8_t*>(ctx->pinned);
     {  // cls[4] @32, bigmeta[2] @48; mid classes 4-6
-      const SmallCopy rb[2] = {{d_cls, 64, 24}, {meta + 64, 88, 4 * kNumMidSub}};
+      const SmallCopy rb[2] = {PXG_PIN_COPY(d_cls, cls), PXG_PIN_COPY(meta + 64, mid_cls)};
       PXG_RETURN_IF_ERROR(ReadbackSmall(ctx, ctx->stream, rb, 2));
     }
     PXG_HIP(hipEventRecord(ctx->ev_meta, ctx->stream));
@@ -1733,20 +1788,20 @@ int32_t AggFinalizeTable(Agg* a) {
     const uint32_t* chain_starts = ws.chain_starts.as<const uint32_t>();
     const int32_t* chain_nc = ws.chain_nc.as<const int32_t>();
     // Chains: latency-bound (one wave per mid / big group, ~110 rounds each), on the side stream.
-    PXG_RETURN_IF_ERROR(ForkSide(ctx));
-    guard.side = true;
-    PXG_RETURN_IF_ERROR(LaunchOn(ctx, ctx->side, "digest_chain", DigestChainKernel, dim3((n_chain_cap + kChainWaves - 1) / kChainWaves),
+    PXG_RETURN_IF_ERROR(ForkSide(ctx, 0));
+    guard.on[0] = true;
+    PXG_RETURN_IF_ERROR(LaunchOn(ctx, ctx->side[0], "digest_chain", DigestChainKernel, dim3((n_chain_cap + kChainWaves - 1) / kChainWaves),
                                  dim3(64 * kChainWaves), 0,
                                  lists + 2 * static_cast<uint64_t>(ngroups), static_cast<const uint32_t*>(d_cls + 2), 0u,
                                  lists + 3 * static_cast<uint64_t>(ngroups), static_cast<const uint32_t*>(d_cls + 3), gstart,
                                  ws.chain_starts.as<uint32_t>(), ws.chain_nc.as<int32_t>()));
-    PXG_HIP(hipEventRecord(ctx->ev_chain, ctx->side));
+    PXG_HIP(hipEventRecord(ctx->ev_chain, ctx->side[0]));
     // The small digests follow the chains on the side stream (neither needs the other); the
     // reductions and the tiny digests run on the main stream meanwhile.
     const uint32_t small_cap = static_cast<uint32_t>(std::min<uint64_t>(ngroups, n / (kTinyMax + 1) + 1));
     for (int u = 0; u < a->n_udas && !a->export_x; ++u) {  // (an export needs no quantiles)
       if (a->uda_kind[u] != PXG_UDA_QUANTILES) continue;
-      PXG_RETURN_IF_ERROR(LaunchOn(ctx, ctx->side, "quant_small", QuantSmallKernel, dim3((small_cap + kSmallWaves - 1) / kSmallWaves),
+      PXG_RETURN_IF_ERROR(LaunchOn(ctx, ctx->side[0], "quant_small", QuantSmallKernel, dim3((small_cap + kSmallWaves - 1) / kSmallWaves),
                                    dim3(256), 0, lists + static_cast<uint64_t>(ngroups), static_cast<const uint32_t*>(d_cls + 1), gstart,
                                    cv.p[a->uda_val[u]], a->uda_arg_type[u], R.uda_out[u].as<double>()));
     }
@@ -1758,7 +1813,7 @@ int32_t AggFinalizeTable(Agg* a) {
     // chain; round 6, tools/step_ab.py at 100M rows: step 2.210 -> 2.173 ms).  With an early set
     // (1B rows) every placement measured the same (14.51-14.58 ms), so they stay on the main
     // stream there, as do the mid classes (on either side stream: 14.56-14.59 ms).
-    const hipStream_t tiny_st = !early_on && guard.side ? ctx->side : ctx->stream;
+    const hipStream_t tiny_st = !early_on && guard.on[0] ? ctx->side[0] : ctx->stream;
     for (int u = 0; u < a->n_udas && !a->export_x; ++u) {
       if (a->uda_kind[u] != PXG_UDA_QUANTILES) continue;
       PXG_RETURN_IF_ERROR(LaunchOn(ctx, tiny_st, "quant_tiny", QuantTinyKernel, dim3((ngroups + 3) / 4), dim3(256), 0, lists,
@@ -1769,30 +1824,17 @@ int32_t AggFinalizeTable(Agg* a) {
     clk.Mark("finalize: issue to meta");
     PXG_HIP(hipEventSynchronize(ctx->ev_meta));
     clk.Mark("finalize: meta wait");
-    std::memcpy(hm, pin + 64, 24);
-    std::memcpy(hmid, pin + 88, 4 * kNumMidSub);
+    static_assert(sizeof(hm) == sizeof(ctx->pinned->cls) && sizeof(hmid) == sizeof(ctx->pinned->mid_cls), "read-back sizes");
+    std::memcpy(hm, ctx->pinned->cls, sizeof(hm));
+    std::memcpy(hmid, ctx->pinned->mid_cls, sizeof(hmid));
     uint32_t cls[kNumClasses] = {hm[0], hm[1], hm[2], hm[3]};
     const uint32_t n_big = cls[3];
     n_big_groups = n_big;
-    SL.big = ws.big.as<BigGroup>();
-    SL.chunks = ws.bchunks.as<BigChunk>();
-    SL.d_count = d_cls + 3;
-    SL.d_meta = d_bigmeta;
+    SL = MakeBigSet(ws.big.as<BigGroup>(), ws.bchunks.as<BigChunk>(), d_cls + 3, d_bigmeta, large_cnt, large_list, chain_starts, chain_nc,
+                    &ws.sel);
     SL.n_big = n_big;
     SL.n_chunks = hm[4];
     SL.big_max = hm[5];
-    SL.chain_starts = chain_starts;
-    SL.chain_nc = chain_nc;
-    SL.spl = &ws.sel_spl;
-    SL.cnt = &ws.sel_cnt;
-    SL.list = &ws.sel_list;
-    SL.bstart = &ws.sel_bstart;
-    SL.tag = &ws.sel_tag;
-    SL.cbase = &ws.sel_cbase;
-    SL.plan = &ws.sel_plan;
-    SL.partial = &ws.sel_partial;
-    SL.large_list = large_list;
-    SL.large_cnt = large_cnt;
     // PXG_BIG_SORT=1 forces the full sort path for every big group (tests compare the two).
     big_select = n_big > 0 && !EnvFlag("PXG_BIG_SORT") && !a->export_x;
     if (big_select) PXG_RETURN_IF_ERROR(EnsureSel(SL));
@@ -1802,26 +1844,18 @@ int32_t AggFinalizeTable(Agg* a) {
     // side stream 2, so later UDAs reuse the workspace safely.
     // With an early set on side stream 2, the late set takes the side stream (behind the small
     // digests), so the two sets' latency-bound chains of launches run side by side.
-    hipStream_t lst = early_on ? ctx->side : ctx->side2;
+    const hipStream_t lst = early_on ? ctx->side[0] : ctx->side[1];
     if (n_big > 0) {
       PXG_HIP(hipStreamWaitEvent(lst, ctx->ev_meta, 0));
-      if (!early_on) guard.side2 = true;
+      if (!early_on) guard.on[1] = true;
     }
     // (Issuing the late set after the mid classes when an early set runs started QuantMid<8192>
     // 0.12 ms sooner at 1B rows but only moved the LDS contention: span 3.96 -> 4.02 ms.)
-    auto IssueLate = [&](int u) -> int32_t {
-      if (big_select) PXG_RETURN_IF_ERROR(BigSelectFront(SL, lst, u));
-      if (n_big > 0) {
-        PXG_HIP(hipStreamWaitEvent(lst, ctx->ev_chain, 0));
-        PXG_RETURN_IF_ERROR(big_select ? BigSelectBack(SL, lst, u) : BigSortPath(SL, lst, u));
-      }
-      return PXG_OK;
-    };
     for (int u = 0; u < a->n_udas; ++u) {
       if (a->uda_kind[u] != PXG_UDA_QUANTILES) continue;
       const uint64_t* vals = cv.p[a->uda_val[u]];
       const int at = a->uda_arg_type[u];
-      PXG_RETURN_IF_ERROR(IssueLate(u));
+      PXG_RETURN_IF_ERROR(IssueLate(lst, u));
       double* qo = R.uda_out[u].as<double>();
       if (!a->export_x) {  // the mid classes, one launch each (largest first: the longest workgroups)
         const uint32_t* cnt_mid = reinterpret_cast<const uint32_t*>(meta + 64);
@@ -1839,12 +1873,18 @@ int32_t AggFinalizeTable(Agg* a) {
                                      static_cast<const uint32_t*>(d_cls + 2), vals, at, qo, d_err));
       }
     }
+    return PXG_OK;
   }
-  if (guard.side) PXG_RETURN_IF_ERROR(JoinSide(ctx));  // the small digests
-  guard.side = false;
-  if (keys_on_side2 || n_big_groups > 0 || early_on) PXG_RETURN_IF_ERROR(JoinSide2(ctx));
-  guard.side2 = false;
-  if (a->export_x) {
+
+  int32_t JoinSides() {
+    if (guard.on[0]) PXG_RETURN_IF_ERROR(JoinSide(ctx, 0));  // the small digests
+    guard.on[0] = false;
+    if (keys_issued || n_big_groups > 0 || early_on) PXG_RETURN_IF_ERROR(JoinSide(ctx, 1));
+    guard.on[1] = false;
+    return PXG_OK;
+  }
+
+  int32_t ExportTail() {
     // An export reads neither the string-key totals nor the result columns: its caller checks
     // the error flag and the device group count (ws.meta) with the readback it waits for anyway
     // (Agg::CheckExportFinalize), so the export finalize ends without a host wait of its own.
@@ -1857,54 +1897,60 @@ int32_t AggFinalizeTable(Agg* a) {
     R.ready = true;
     return PXG_OK;
   }
+
   // Early result: quantile columns asked for as plucked lanes, behind the digests, so their
   // copies land within the synchronisation below.
-  auto IssueEarlyLanes = [&]() -> int32_t {
+  int32_t IssueEarlyLanes() {
     if (!a->early.want || !a->early.skip || a->merged) return PXG_OK;
     for (int u = 0; u < a->n_udas; ++u) {
       const uint8_t sk = a->early.skip[a->n_keys + u];
       if (a->uda_kind[u] == PXG_UDA_QUANTILES && (sk & kSkipLanes)) PXG_RETURN_IF_ERROR(IssueLanes(*a, u, sk, a->early.cols[a->n_keys + u]));
     }
     return PXG_OK;
-  };
-  PXG_RETURN_IF_ERROR(IssueEarlyLanes());
-  // One sync for the digest error flag and every string-key total.
-  std::vector<uint32_t> totals(kMaxKeys, 0);
-  unsigned int err = 0;
-  uint32_t* pin32 = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ctx->pinned) + 128);
-  uint32_t g_dev = 0;
-  {  // one launch for the string-key totals, the error / group count / fallback words, early meta
-    SmallCopy rb[kMaxSmallCopies];
-    int nrb = 0;
-    const uint32_t b = 128;  // pin32's byte offset in the pinned scratch
-    for (int k = 0; k < a->n_keys; ++k)
-      if (a->key_types[k] == PXG_STRING) rb[nrb++] = {R.key_offsets[k].as<uint32_t>() + ngroups, b + 4 * k, 4};
-    rb[nrb++] = {d_err, b + 4 * kMaxKeys, 4};
-    rb[nrb++] = {d_ngroups, b + 4 * (kMaxKeys + 1), 4};
-    rb[nrb++] = {d_fallback, b + 4 * (kMaxKeys + 2), 4};
-    if (early_on) rb[nrb++] = {ws.early.meta.p, b + 4 * (kMaxKeys + 3), 12};
-    PXG_RETURN_IF_ERROR(ReadbackSmall(ctx, ctx->stream, rb, nrb));
   }
-  clk.Mark("finalize: issue rest");
-  PXG_HIP(hipStreamSynchronize(ctx->stream));
-  clk.Mark("finalize: final wait");
-  for (int k = 0; k < a->n_keys; ++k)
-    if (a->key_types[k] == PXG_STRING) totals[k] = pin32[k];
-  err = pin32[kMaxKeys];
-  g_dev = pin32[kMaxKeys + 1];
-  const bool any_select = big_select || early_on;
-  const uint32_t n_fallback = any_select ? pin32[kMaxKeys + 2] : 0;
-  a->last_big_sort_groups = any_select ? n_fallback : n_big_groups;
-  if (any_select && n_fallback > 0) {
+
+  // One sync for the digest error flag, every string-key total, the group count and the
+  // selection sets' fallback count.
+  int32_t FinalReadback() {
+    PXG_RETURN_IF_ERROR(IssueEarlyLanes());
+    {  // one launch for the string-key totals, the error / group count / fallback words, early meta
+      static_assert(kMaxKeys + 4 <= kMaxSmallCopies, "the final read-back is one ReadbackSmall launch");
+      SmallCopy rb[kMaxSmallCopies];
+      int nrb = 0;
+      for (int k = 0; k < a->n_keys; ++k) {
+        if (a->key_types[k] != PXG_STRING) continue;
+        rb[nrb] = PXG_PIN_COPY(R.key_offsets[k].as<uint32_t>() + ngroups, key_totals[0]);
+        rb[nrb++].dst_off += 4 * k;
+      }
+      rb[nrb++] = PXG_PIN_COPY(d_err, err);
+      rb[nrb++] = PXG_PIN_COPY(d_ngroups, ngroups);
+      rb[nrb++] = PXG_PIN_COPY(d_fallback, fallback);
+      if (early_on) rb[nrb++] = PXG_PIN_COPY(ws.early.meta.p, early_meta);
+      PXG_RETURN_IF_ERROR(ReadbackSmall(ctx, ctx->stream, rb, nrb));
+    }
+    clk.Mark("finalize: issue rest");
+    PXG_HIP(hipStreamSynchronize(ctx->stream));
+    clk.Mark("finalize: final wait");
+    const PinnedScratch& pin = *ctx->pinned;
+    err = pin.err;
+    g_dev = pin.ngroups;
+    const bool any_select = big_select || early_on;
+    n_fallback = any_select ? pin.fallback : 0;
+    a->last_big_sort_groups = any_select ? n_fallback : n_big_groups;
+    return PXG_OK;
+  }
+
+  int32_t Fallback() {
+    PinnedScratch& pin = *ctx->pinned;
     // Some big group could not be served by selection (NaN values, a gathered bin past its
     // capacity: heavy ties).  With one quantile UDA the full sort path recomputes just those
     // groups (both sets' flagged groups as one set: their list, BigSetup and chains, then the
     // chunk sort / merges / digests); with several, every big group of both sets (the plans hold
     // the last UDA's flags only).  The chains and the sets' work are long done.
     if (early_on) {
-      SE.n_big = pin32[kMaxKeys + 3];
-      SE.n_chunks = pin32[kMaxKeys + 4];
-      SE.big_max = pin32[kMaxKeys + 5];
+      SE.n_big = pin.early_meta[0];
+      SE.n_chunks = pin.early_meta[1];
+      SE.big_max = pin.early_meta[2];
     }
     int nq = 0;
     for (int u = 0; u < a->n_udas; ++u) nq += a->uda_kind[u] == PXG_UDA_QUANTILES ? 1 : 0;
@@ -1920,24 +1966,19 @@ int32_t AggFinalizeTable(Agg* a) {
         PXG_RETURN_IF_ERROR(SelFallbackList(ctx, *S, fl, fm));
       }
       // The subset in the late set's buffers (sized for every group above kMidMax values).
-      BigSet SF;
-      SF.big = ws.big.as<BigGroup>();
-      SF.chunks = ws.bchunks.as<BigChunk>();
-      SF.d_count = fm;
-      SF.d_meta = fm + 1;
-      SF.chain_starts = ws.chain_starts.as<const uint32_t>();
-      SF.chain_nc = ws.chain_nc.as<const int32_t>();
-      uint32_t* large_list = reinterpret_cast<uint32_t*>(ws.big.as<uint8_t>() + (n / (kMidMax + 1) + 1) * sizeof(BigGroup)) + 4;
+      uint32_t* large_list = LateLargeCnt() + 4;
+      BigSet SF = MakeBigSet(ws.big.as<BigGroup>(), ws.bchunks.as<BigChunk>(), fm, fm + 1, fm + 3, large_list,
+                             ws.chain_starts.as<const uint32_t>(), ws.chain_nc.as<const int32_t>(), &ws.sel);
       PXG_RETURN_IF_ERROR(Launch(ctx, "big_setup", BigSetupKernel, dim3(1), dim3(kSetupBlock), 0, static_cast<const uint32_t*>(fl),
                                  static_cast<const uint32_t*>(fm), gstart, SF.big, SF.chunks, fm + 1, large_list, fm + 3));
       PXG_RETURN_IF_ERROR(Launch(ctx, "digest_chain", DigestChainKernel, dim3((cap_fb + kChainWaves - 1) / kChainWaves), dim3(64 * kChainWaves), 0,
                                  static_cast<const uint32_t*>(fl), static_cast<const uint32_t*>(fm), 0u, static_cast<const uint32_t*>(fl),
                                  static_cast<const uint32_t*>(fm), gstart, ws.chain_starts.as<uint32_t>(), ws.chain_nc.as<int32_t>()));
-      PXG_HIP(hipMemcpyAsync(pin32 + kMaxKeys + 6, fm, 12, hipMemcpyDeviceToHost, ctx->stream));
+      PXG_HIP(hipMemcpyAsync(pin.fb_meta, fm, sizeof(pin.fb_meta), hipMemcpyDeviceToHost, ctx->stream));
       PXG_HIP(hipStreamSynchronize(ctx->stream));
-      SF.n_big = pin32[kMaxKeys + 6];
-      SF.n_chunks = pin32[kMaxKeys + 7];
-      SF.big_max = pin32[kMaxKeys + 8];
+      SF.n_big = pin.fb_meta[0];
+      SF.n_chunks = pin.fb_meta[1];
+      SF.big_max = pin.fb_meta[2];
       for (int u = 0; u < a->n_udas; ++u)
         if (a->uda_kind[u] == PXG_UDA_QUANTILES && SF.n_big > 0) PXG_RETURN_IF_ERROR(BigSortPath(SF, ctx->stream, u));
     } else {
@@ -1949,20 +1990,40 @@ int32_t AggFinalizeTable(Agg* a) {
       }
     }
     PXG_RETURN_IF_ERROR(IssueEarlyLanes());  // the recomputed groups' lanes
-    PXG_HIP(hipMemcpyAsync(pin32 + kMaxKeys, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
+    PXG_HIP(hipMemcpyAsync(&pin.err, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
     PXG_HIP(hipStreamSynchronize(ctx->stream));
-    err = pin32[kMaxKeys];
+    err = pin.err;
+    return PXG_OK;
   }
-  if (err) return SetError(PXG_INTERNAL, "t-digest centroid capacity exceeded");
-  a->x_vals = a->x_qval >= 0 ? cv.p[a->x_qval] : nullptr;
-  a->x_wts = a->merged ? cv.p[a->n_vals] : nullptr;
-  a->x_nbig = n_big_groups;
-  if (g_dev != ngroups) return SetError(PXG_INTERNAL, "group table holds %u groups, host mirror says %u", g_dev, ngroups);
-  for (int k = 0; k < a->n_keys; ++k)
-    if (a->key_types[k] == PXG_STRING) R.key_data_len[k] = totals[k];
-  PXG_HIP(hipStreamSynchronize(ctx->stream));
-  R.ready = true;
-  return PXG_OK;
+
+  int32_t Finish() {
+    if (err) return SetError(PXG_INTERNAL, "t-digest centroid capacity exceeded");
+    a->x_vals = a->x_qval >= 0 ? cv.p[a->x_qval] : nullptr;
+    a->x_wts = a->merged ? cv.p[a->n_vals] : nullptr;
+    a->x_nbig = n_big_groups;
+    if (g_dev != ngroups) return SetError(PXG_INTERNAL, "group table holds %u groups, host mirror says %u", g_dev, ngroups);
+    for (int k = 0; k < a->n_keys; ++k)
+      if (a->key_types[k] == PXG_STRING) R.key_data_len[k] = ctx->pinned->key_totals[k];
+    PXG_HIP(hipStreamSynchronize(ctx->stream));
+    R.ready = true;
+    return PXG_OK;
+  }
+};
+
+int32_t AggFinalizeTable(Agg* a) {
+  TableFinalize f(a);
+  PXG_RETURN_IF_ERROR(f.Prepare());
+  if (f.R.ready) return PXG_OK;
+  PXG_RETURN_IF_ERROR(f.Grouping());
+  PXG_RETURN_IF_ERROR(f.ReductionSetup());
+  if (!f.any_q) PXG_RETURN_IF_ERROR(f.RunReductions());
+  if (f.early_on) PXG_RETURN_IF_ERROR(f.EarlySet());
+  if (f.any_q) PXG_RETURN_IF_ERROR(f.Digests());
+  PXG_RETURN_IF_ERROR(f.JoinSides());
+  if (a->export_x) return f.ExportTail();
+  PXG_RETURN_IF_ERROR(f.FinalReadback());
+  if (f.n_fallback > 0) PXG_RETURN_IF_ERROR(f.Fallback());
+  return f.Finish();
 }
 
 }  // namespace pxg
@@ -2011,17 +2072,10 @@ extern "C" int32_t pxg_agg_quantile_lanes(pxg_agg* agg, int32_t uda, uint32_t la
   if (!a.res.ready) return SetError(PXG_FAILED_PRECONDITION, "pxg_agg_finalize has not run since the last consume");
   if (uda < 0 || uda >= a.n_udas || a.uda_kind[uda] != PXG_UDA_QUANTILES)
     return SetError(PXG_INVALID_ARGUMENT, "aggregate %d is not a quantiles UDA", uda);
-  lane_mask &= 0x7Fu;
-  const int nsel = __builtin_popcount(lane_mask);
-  const uint64_t G = static_cast<uint64_t>(a.res.n_groups);
-  if (G == 0) return PXG_OK;
-  PXG_RETURN_IF_ERROR(a.res.lanes.Ensure(G * (8 * nsel + 1) + 16));
-  double* d_out = a.res.lanes.as<double>();
-  uint8_t* d_fin = reinterpret_cast<uint8_t*>(d_out + G * nsel);
-  PXG_RETURN_IF_ERROR(Launch(a.ctx, "quant_lanes", QuantLanesKernel, dim3(GridFor(static_cast<int64_t>(G), 256, 1 << 30)), dim3(256), 0,
-                             a.res.uda_out[uda].as<const double>(), G, lane_mask, d_out, d_fin));
-  if (nsel) PXG_RETURN_IF_ERROR(CopyD2H(a.ctx, a.ctx->stream, host_out, d_out, G * nsel * 8));
-  PXG_RETURN_IF_ERROR(CopyD2H(a.ctx, a.ctx->stream, host_finite, d_fin, G));
+  pxg_column_out o{};  // the caller's buffers: IssueLanes allocates none
+  o.values = host_out;
+  o.data = host_finite;
+  PXG_RETURN_IF_ERROR(IssueLanes(a, uda, lane_mask, o));
   PXG_HIP(hipStreamSynchronize(a.ctx->stream));
   return PXG_OK;
 }
@@ -2133,32 +2187,8 @@ extern "C" int32_t pxg_agg_result_skip(pxg_agg* agg, pxg_column_out* cols, int32
     ~DrainOnExit() { (void)hipStreamSynchronize(s); }
   } drain{a.ctx->stream};
   for (int c = 0; c < n_cols; ++c) std::memset(&cols[c], 0, sizeof(cols[c]));
-  for (int k = 0; k < a.n_keys; ++k) {
-    pxg_column_out& o = cols[k];
-    o.type = a.key_types[k];
-    o.length = rows;
-    if (o.type == PXG_STRING) {
-      o.offsets = static_cast<int32_t*>(ResultAlloc((rows + 1) * 4));
-      o.data = static_cast<uint8_t*>(ResultAlloc(a.res.key_data_len[k] + 16));
-      o.data_len = a.res.key_data_len[k];
-      if (G > 0) {
-        PXG_RETURN_IF_ERROR(CopyD2H(a.ctx, a.ctx->stream, o.offsets, a.res.key_offsets[k].p, (G + 1) * 4));
-        PXG_RETURN_IF_ERROR(CopyD2H(a.ctx, a.ctx->stream, o.data, a.res.key_data[k].p, o.data_len));
-      } else {
-        o.offsets[0] = 0;
-      }
-    } else {
-      const size_t w = TypeWidth(o.type);
-      o.values = ResultAlloc(std::max<size_t>(rows * w, 1));
-      if (G > 0) {
-        if (o.type == PXG_BOOLEAN) {
-          PXG_RETURN_IF_ERROR(CopyD2H(a.ctx, a.ctx->stream, o.values, a.res.key_fixed[k].p, G));
-        } else {
-          PXG_RETURN_IF_ERROR(CopyD2H(a.ctx, a.ctx->stream, o.values, a.res.key_fixed[k].p, G * w));
-        }
-      }
-    }
-  }
+  for (int k = 0; k < a.n_keys; ++k)  // (with keys, rows == G)
+    PXG_RETURN_IF_ERROR(IssueKeyColumn(a, k, a.ctx->stream, static_cast<size_t>(a.res.key_data_len[k]), cols[k]));
   if (a.emit_states) {  // serialized_expressions: fixed-size records (operators.cc:251-257)
     pxg_column_out& o = cols[a.n_keys];
     o.type = PXG_STRING;
@@ -2167,6 +2197,7 @@ extern "C" int32_t pxg_agg_result_skip(pxg_agg* agg, pxg_column_out* cols, int32
     o.offsets = static_cast<int32_t*>(ResultAlloc((rows + 1) * 4));
     o.data = static_cast<uint8_t*>(ResultAlloc(rows * rec + 16));
     o.data_len = rows * rec;
+    if (!o.offsets || !o.data) return SetError(PXG_RESOURCE_UNAVAILABLE, "host result allocation failed");
     for (int64_t g = 0; g <= rows; ++g) o.offsets[g] = static_cast<int32_t>(g * rec);
     if (!synth) {
       if (G > 0 && rec > 0) PXG_RETURN_IF_ERROR(CopyD2H(a.ctx, a.ctx->stream, o.data, a.res.states.p, G * rec));
@@ -2198,6 +2229,7 @@ extern "C" int32_t pxg_agg_result_skip(pxg_agg* agg, pxg_column_out* cols, int32
     const bool q = a.uda_kind[u] == PXG_UDA_QUANTILES;
     const size_t per = q ? 56 : 8;
     o.values = ResultAlloc(std::max<size_t>(rows * per, 8));
+    if (!o.values) return SetError(PXG_RESOURCE_UNAVAILABLE, "host result allocation failed");
     if (!synth) {
       PXG_RETURN_IF_ERROR(CopyD2H(a.ctx, a.ctx->stream, o.values, a.res.uda_out[u].p, G * per));
       continue;
@@ -2229,7 +2261,7 @@ int32_t pxg::LaunchDigestMerge(Agg* a, const uint32_t* dlist, const uint32_t* dc
                                ws.gstart.as<const uint32_t>(), a->x_vals, a->x_wts, a->uda_arg_type[u], k0, k0 + n, k0 + 2 * n, k0 + 3 * n,
                                a->res.uda_out[u].as<double>(), d_err));
   }
-  uint32_t* pin = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ctx->pinned) + 120);
+  uint32_t* pin = &ctx->pinned->merged_flags;
   PXG_HIP(hipMemcpyAsync(pin, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
   PXG_HIP(hipStreamSynchronize(ctx->stream));
   if (*pin) return SetError(PXG_INTERNAL, "merged digest overflow (flags %u)", *pin);

@@ -1003,9 +1003,8 @@ int32_t FusedSplitPass(Ctx* ctx, const uint32_t* st_slot, uint64_t n, const uint
   PXG_RETURN_IF_ERROR(Launch(ctx, "radix_scan", XDownKernel<kFsBuckets>, dim3(nparts), dim3(256), 0, hist, ntiles,
                              static_cast<const uint32_t*>(rs.part.as<uint32_t>()), static_cast<const uint32_t*>(base)));
   // n_rest (= base[kFsRest]) and the designated count to pinned memory; the scatter runs meanwhile.
-  uint8_t* pin = static_cast<uint8_t*>(ctx->pinned);
-  PXG_HIP(hipMemcpyAsync(pin + 104, base + kFsRest, 4, hipMemcpyDeviceToHost, ctx->stream));
-  PXG_HIP(hipMemcpyAsync(pin + 112, d_ftotal, 8, hipMemcpyDeviceToHost, ctx->stream));
+  PXG_HIP(hipMemcpyAsync(&ctx->pinned->split_n_rest, base + kFsRest, 4, hipMemcpyDeviceToHost, ctx->stream));
+  PXG_HIP(hipMemcpyAsync(&ctx->pinned->split_ftotal, d_ftotal, 8, hipMemcpyDeviceToHost, ctx->stream));
   PXG_HIP(hipEventRecord(ctx->ev_split, ctx->stream));
   PXG_RETURN_IF_ERROR(Launch(ctx, "radix_scatter", FsScatterKernel, dim3(ntiles), dim3(kFsBlock), 0, static_cast<const uint32_t*>(fs_keys.as<uint32_t>()),
                              n, G, d_ftotal, vin, nvs, static_cast<const uint32_t*>(hist), kout_rest, vrest, vfin));

@@ -576,7 +576,7 @@ int32_t Agg::FinalizeHc(HcExport* ex) {
   const size_t lds = HcAggLdsBytes(hp.nacc, hp.nhi);
   if (lds > HcMaxDynLds()) return SetError(PXG_INTERNAL, "hc_agg needs %zu bytes of LDS", lds);
   uint32_t* meta = w.hc_meta.as<uint32_t>();
-  uint32_t* pin = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ctx->pinned) + 192);
+  uint32_t* pin = ctx->pinned->hc_meta;
   // The first pass aims at ~2^kHcGroupsLog2 groups per partition (a half-full LDS table) from
   // the expected group count: the hint or the last run (both count every group), else the
   // records (all distinct).  Sizing by records alone gave ~1024 groups per partition for
@@ -657,7 +657,7 @@ int32_t Agg::FinalizeHc(HcExport* ex) {
     kc.data[k] = R.key_data[k].as<uint8_t>();
     kc.dbase[k] = static_cast<uint32_t>(dbase[k]);
   }
-  uint32_t* pin32 = pin + 4;
+  uint32_t* pin32 = ctx->pinned->hc_key_totals;
   if (any_str && G > 0) {
     PXG_RETURN_IF_ERROR(Launch(ctx, "hc_key_copy", HcKeyCopyKernel, dim3(GridFor(static_cast<int64_t>(G) + 1, 256, 1 << 30)), dim3(256), 0,
                                static_cast<const uint64_t*>(out.kscr), hp.n, G, n_keys, kc, hp));
@@ -808,13 +808,13 @@ int32_t Agg::SpillHc() {
                              arena.as<const uint64_t>(), slots.as<unsigned long long>(), cap - 1,
                              st_slot.as<uint32_t>(), stg, n_vals, counters.as<unsigned int>()));
   arena_words = abase + n * rec_words;
-  uint8_t* pin = static_cast<uint8_t*>(ctx->pinned) + 224;
-  PXG_HIP(hipMemcpyAsync(pin, cb, 40, hipMemcpyDeviceToHost, ctx->stream));
+  uint8_t* hcb = ctx->pinned->hc_spill;  // the counters on the host: groups @0, staging cursor @16, error flags @36
+  PXG_HIP(hipMemcpyAsync(hcb, cb, sizeof(ctx->pinned->hc_spill), hipMemcpyDeviceToHost, ctx->stream));
   PXG_HIP(hipStreamSynchronize(ctx->stream));
   uint32_t groups = 0, err = 0;
-  std::memcpy(&groups, pin, 4);
-  std::memcpy(&err, pin + 36, 4);
-  std::memcpy(&st_n, pin + 16, 8);
+  std::memcpy(&groups, hcb, 4);
+  std::memcpy(&err, hcb + 36, 4);
+  std::memcpy(&st_n, hcb + 16, 8);
   if (err) return SetError(PXG_INTERNAL, "group table full while spilling partition records");
   inserted = groups;
   state_version++;

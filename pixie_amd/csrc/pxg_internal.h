@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +12,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pxg.h"
@@ -59,33 +61,14 @@ struct DevBuf {
   }
   int32_t Alloc(size_t n) {
     Free();
-    if (n == 0) n = 16;
-    hipError_t e = hipMalloc(&p, n);
-    if (e != hipSuccess) {
-      p = nullptr;
-      return SetError(PXG_RESOURCE_UNAVAILABLE, "hipMalloc(%zu) failed: %s", n, hipGetErrorString(e));
-    }
-    bytes = n;
-    return PXG_OK;
+    return ReserveExact(n ? n : 16, 0, nullptr);
   }
   // Ensure capacity >= n, preserving the first `keep` bytes (stream-ordered copy).
   int32_t Reserve(size_t n, size_t keep, hipStream_t s) {
     if (n <= bytes) return PXG_OK;
     size_t cap = bytes ? bytes : 256;
     while (cap < n) cap *= 2;
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, cap);
-    if (e != hipSuccess) return SetError(PXG_RESOURCE_UNAVAILABLE, "hipMalloc(%zu) failed: %s", cap, hipGetErrorString(e));
-    if (keep && p) {
-      e = hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, s);
-      if (e != hipSuccess) return SetError(PXG_INTERNAL, "hipMemcpyAsync failed: %s", hipGetErrorString(e));
-      e = hipStreamSynchronize(s);
-      if (e != hipSuccess) return SetError(PXG_INTERNAL, "sync failed: %s", hipGetErrorString(e));
-    }
-    Free();
-    p = q;
-    bytes = cap;
-    return PXG_OK;
+    return ReserveExact(cap, keep, s);
   }
   // Capacity >= n without power-of-two rounding (the caller picks the growth policy).
   int32_t ReserveExact(size_t n, size_t keep, hipStream_t s) {
@@ -135,17 +118,49 @@ struct BufPool {
   size_t cap = size_t(16) << 30;
 };
 
+// Layout of the context's pinned read-back scratch: one member per reader, none shared, so an
+// asynchronous read-back never lands in words another phase is still reading.
+constexpr size_t kPinnedOps = 4096, kPinnedBytes = 65536;
+struct PinnedScratch {
+  // consume publish (Agg::PublishNew)
+  uint64_t publish_total;         // new groups << kPublishCountShift | arena words
+  uint8_t publish_counters[56];   // Agg::counters
+  uint32_t hc_maxlen[kMaxKeys];
+  // finalize (AggFinalizeTable)
+  uint32_t cls[6];                // class counts [4], big chunks, largest big group
+  uint32_t mid_cls[3];            // mid sub-class counts (kNumMidSub)
+  uint32_t split_n_rest;          // fused split: the rest records ...
+  uint64_t split_ftotal;          // ... and its designation total (FusedSplitPass, ev_split)
+  uint32_t key_totals[kMaxKeys];  // STRING key payload bytes
+  uint32_t err, ngroups, fallback;
+  uint32_t early_meta[3];         // early set: groups, chunks, largest group
+  uint32_t fb_meta[3];            // fallback set: the same
+  uint32_t merged_flags;          // LaunchDigestMerge
+  // high-cardinality finalize / spill (pxg_hc.hip)
+  uint32_t hc_meta[2];            // groups, overflowed partitions
+  uint32_t hc_key_totals[kMaxKeys];
+  alignas(8) uint8_t hc_spill[40];  // Agg::counters after the spill
+  // partial import (pxg_partial.hip)
+  uint32_t import_meta[2];        // inserts, error flags
+  uint64_t import_cursor;         // host -> device: the staging cursor
+  uint64_t pxrb_bytes;            // the device result image's size (pxg_pxrb.hip)
+  // standalone Filter / Map / Join per-chunk counts, exchange headers
+  alignas(kPinnedOps) uint8_t ops[kPinnedBytes - kPinnedOps];
+};
+static_assert(std::is_standard_layout<PinnedScratch>::value && std::is_trivial<PinnedScratch>::value, "plain old data");
+static_assert(sizeof(PinnedScratch) == kPinnedBytes, "the pinned scratch is allocated as kPinnedBytes");
+static_assert(offsetof(PinnedScratch, ops) == kPinnedOps, "the ops area starts at kPinnedOps");
+
 struct Ctx {
   int device = 0;
   OpsWorkspace ops;
   BufPool pool;
   hipStream_t stream = nullptr;
-  // Side stream for latency-bound work that overlaps the main stream (fork/join by events).
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  // Second side stream: the big-group quantile merges overlap the mid digests and the key output.
-  hipStream_t side2 = nullptr;
-  hipEvent_t ev_fork2 = nullptr, ev_join2 = nullptr;
+  // Side streams for latency-bound work that overlaps the main stream (fork/join by events).
+  // side[1] ("side stream 2", a priority stream): the big-group quantile merges overlap the mid
+  // digests and the key output.
+  hipStream_t side[2] = {nullptr, nullptr};
+  hipEvent_t ev_fork[2] = {nullptr, nullptr}, ev_join[2] = {nullptr, nullptr};
   hipEvent_t ev_meta = nullptr;  // finalize: the big-group metadata readback has landed
   hipEvent_t ev_chain = nullptr; // finalize: the digest boundary chains are done (side stream)
   hipEvent_t ev_split = nullptr; // finalize: the staging split's bucket totals have landed (pinned)
@@ -157,13 +172,9 @@ struct Ctx {
   std::vector<PendingTiming> pending;
   std::vector<hipEvent_t> free_events;
   int num_cus = 256;
-  // Pinned scratch for counters read back by the host (async D2H, no staging copy):
-  // [0, 64) consume publish, [64, 104) finalize class counts, [104, 128) finalize split
-  // totals, [128, 256) finalize totals (HC / export phases reuse [192, 256)), [256, 264) the
-  // device result image's size (pxg_pxrb.hip),
-  // [kPinnedOps, kPinnedBytes) standalone Filter / Map per-chunk counts.
-  void* pinned = nullptr;
-  static constexpr size_t kPinnedOps = 4096, kPinnedBytes = 65536;
+  // Pinned scratch for counters read back by the host (async D2H, no staging copy).
+  PinnedScratch* pinned = nullptr;
+  static constexpr size_t kPinnedOps = pxg::kPinnedOps, kPinnedBytes = pxg::kPinnedBytes;
   // Finalize: t-digest boundary chains of every mid-class group size (a pure function of the
   // size; pxg_finalize.hip EnsureMidChains), built on first use.
   DevBuf mid_chains;
@@ -228,28 +239,19 @@ inline int32_t Launch(Ctx* ctx, const char* name, void (*kernel)(KArgs...), dim3
   return LaunchOn(ctx, ctx->stream, name, kernel, grid, block, shmem, std::forward<Args>(args)...);
 }
 
-// Fork the side stream off the main stream / join it back.
-inline int32_t ForkSide(Ctx* ctx) {
-  if (hipEventRecord(ctx->ev_fork, ctx->stream) != hipSuccess || hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0) != hipSuccess)
-    return SetError(PXG_INTERNAL, "side stream fork failed");
-  return PXG_OK;
+// Fork side stream i off the main stream / join it back: `waiter` continues after what
+// `signaller` holds now.
+inline int32_t StreamAfter(hipStream_t waiter, hipEvent_t ev, hipStream_t signaller, const char* what, int i) {
+  const char* call = "hipEventRecord";
+  hipError_t e = hipEventRecord(ev, signaller);
+  if (e == hipSuccess) {
+    call = "hipStreamWaitEvent";
+    e = hipStreamWaitEvent(waiter, ev, 0);
+  }
+  return e == hipSuccess ? PXG_OK : SetError(PXG_INTERNAL, "side stream [%d] %s: %s failed: %s", i, what, call, hipGetErrorName(e));
 }
-inline int32_t JoinSide(Ctx* ctx) {
-  if (hipEventRecord(ctx->ev_join, ctx->side) != hipSuccess || hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0) != hipSuccess)
-    return SetError(PXG_INTERNAL, "side stream join failed");
-  return PXG_OK;
-}
-
-inline int32_t ForkSide2(Ctx* ctx) {
-  if (hipEventRecord(ctx->ev_fork2, ctx->stream) != hipSuccess || hipStreamWaitEvent(ctx->side2, ctx->ev_fork2, 0) != hipSuccess)
-    return SetError(PXG_INTERNAL, "side stream 2 fork failed");
-  return PXG_OK;
-}
-inline int32_t JoinSide2(Ctx* ctx) {
-  if (hipEventRecord(ctx->ev_join2, ctx->side2) != hipSuccess || hipStreamWaitEvent(ctx->stream, ctx->ev_join2, 0) != hipSuccess)
-    return SetError(PXG_INTERNAL, "side stream 2 join failed");
-  return PXG_OK;
-}
+inline int32_t ForkSide(Ctx* ctx, int i) { return StreamAfter(ctx->side[i], ctx->ev_fork[i], ctx->stream, "fork", i); }
+inline int32_t JoinSide(Ctx* ctx, int i) { return StreamAfter(ctx->stream, ctx->ev_join[i], ctx->side[i], "join", i); }
 
 inline int GridFor(int64_t items, int per_block, int cap) {
   int64_t g = (items + per_block - 1) / per_block;
@@ -326,6 +328,14 @@ struct SmallCopy {
   uint32_t bytes;
 };
 constexpr int kMaxSmallCopies = 8;
+// The copy of a device value into PinnedScratch member m (a whole member, or one array element),
+// checked against the limits above.
+template <size_t kOff, size_t kBytes>
+inline SmallCopy PinCopyAt(const void* src) {
+  static_assert(kOff % 4 == 0 && kBytes % 4 == 0 && kBytes <= 64, "ReadbackSmall: 4-byte aligned, at most 64 bytes");
+  return {src, static_cast<uint32_t>(kOff), static_cast<uint32_t>(kBytes)};
+}
+#define PXG_PIN_COPY(src, m) ::pxg::PinCopyAt<offsetof(::pxg::PinnedScratch, m), sizeof(::pxg::PinnedScratch::m)>(src)
 int32_t ReadbackSmall(Ctx* ctx, hipStream_t stream, const SmallCopy* items, int n);
 // Zero up to four device ranges (4-byte aligned, sizes multiples of 4) in one launch.
 int32_t ZeroRanges(Ctx* ctx, hipStream_t stream, void* const* ptrs, const size_t* bytes, int n);

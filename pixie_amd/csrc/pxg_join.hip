@@ -380,7 +380,7 @@ static int32_t JoinImpl(Table& B, Table& P, const pxg_join_spec& sp, pxg_table**
     }
   } back_out{ctx, bufs};
   std::vector<pxg_column_view> views(sp.n_out);
-  uint32_t* pin = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ctx->pinned) + Ctx::kPinnedOps);
+  uint32_t* pin = reinterpret_cast<uint32_t*>(ctx->pinned->ops);
   if (static_cast<size_t>(sp.n_out) * 4 > Ctx::kPinnedBytes - Ctx::kPinnedOps) return SetError(PXG_UNIMPLEMENTED, "too many join outputs");
   int n_str = 0;
   for (int i = 0; i < sp.n_out; ++i) {

@@ -546,7 +546,7 @@ static int32_t FilterImpl(Table& t, const pxg_program& pred, int32_t n_select, c
   // pinned: [0, P) selected rows, then per (part, STRING column) the input byte range (2 words)
   // and the output bytes (2 words, the look-back's u64 inclusive prefix)
   if (parts.size() * (2 + 4 * static_cast<size_t>(fs.n_str)) + 2 > pin_cap) return SetError(PXG_UNIMPLEMENTED, "filter over %zu chunks", parts.size());
-  uint32_t* pin = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ctx->pinned) + Ctx::kPinnedOps);
+  uint32_t* pin = reinterpret_cast<uint32_t*>(ctx->pinned->ops);
   pxg_table* ot = nullptr;
   PXG_RETURN_IF_ERROR(NewTable(ctx, static_cast<int32_t>(otypes.size()), otypes.data(), &ot));
   std::unique_ptr<pxg_table, int32_t (*)(pxg_table*)> guard(ot, pxg_table_destroy);
@@ -760,7 +760,7 @@ extern "C" int32_t pxg_map(pxg_table* inp, int32_t n_exprs, const pxg_program* e
     if (lo < hi) parts.push_back({c, lo, hi - lo});
   }
   // Passed-through STRING columns: every chunk's first / last offset in one readback.
-  uint32_t* pin = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ctx->pinned) + Ctx::kPinnedOps);
+  uint32_t* pin = reinterpret_cast<uint32_t*>(ctx->pinned->ops);
   if (n_str_pass > 0) {
     if (parts.size() * n_str_pass * 2 > (Ctx::kPinnedBytes - Ctx::kPinnedOps) / 4)
       return SetError(PXG_UNIMPLEMENTED, "map over %zu chunks", parts.size());

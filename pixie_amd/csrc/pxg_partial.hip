@@ -542,7 +542,7 @@ int32_t Agg::ImportPartials(const void* src, int32_t n, const int64_t* offs, con
     r0 += h.n_rows;
   }
   arena_words = kw;
-  uint32_t* pin = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ctx->pinned) + 240);
+  uint32_t* pin = ctx->pinned->import_meta;
   PXG_HIP(hipMemcpyAsync(pin, meta + 32, 8, hipMemcpyDeviceToHost, ctx->stream));
   PXG_HIP(hipStreamSynchronize(ctx->stream));
   const uint32_t r_ins = pin[0], r_err = pin[1];
@@ -551,7 +551,7 @@ int32_t Agg::ImportPartials(const void* src, int32_t n, const int64_t* offs, con
   inserted += r_ins;
   st_n += tot_rows;
   // Keep the device fill counter and staging cursor exact (the consume kernel reads both).
-  uint64_t* pin64 = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(ctx->pinned) + 248);
+  uint64_t* pin64 = &ctx->pinned->import_cursor;
   *pin64 = st_n;
   PXG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(counters.p), static_cast<int>(inserted), 1, ctx->stream));
   PXG_HIP(hipMemcpyAsync(counters.as<uint8_t>() + 16, pin64, 8, hipMemcpyHostToDevice, ctx->stream));
@@ -1297,7 +1297,7 @@ int32_t Agg::ImportPartialsV2(const uint8_t* base8, int32_t n, const int64_t* of
     g0 += h.n_groups;
   }
   arena_words = kw;
-  uint32_t* pin = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ctx->pinned) + 240);
+  uint32_t* pin = ctx->pinned->import_meta;
   PXG_HIP(hipMemcpyAsync(pin, meta + 32, 8, hipMemcpyDeviceToHost, ctx->stream));
   PXG_HIP(hipStreamSynchronize(ctx->stream));
   const uint32_t r_ins = pin[0], r_err = pin[1];

@@ -143,7 +143,7 @@ extern "C" int32_t pxg_table_pxrb_image(pxg_table* tp, const int64_t* starts, in
                              d_starts.as<const int64_t>(), n_batches, sizes.as<uint64_t>()));
   uint64_t* boff = sizes.as<uint64_t>();
   PXG_RETURN_IF_ERROR(ScanExclusiveU64(ctx, boff, boff, n_batches, boff + n_batches, scan.p));
-  uint64_t* pin = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(ctx->pinned) + 256);
+  uint64_t* pin = &ctx->pinned->pxrb_bytes;
   PXG_HIP(hipMemcpyAsync(pin, boff + n_batches, 8, hipMemcpyDeviceToHost, ctx->stream));
   PXG_HIP(hipStreamSynchronize(ctx->stream));
   const uint64_t total = *pin;

@@ -6,6 +6,7 @@
 // HBM-resident image of those batches, coalesced into <= 2^24-row chunks so the operators see
 // a few large Arrow-layout arrays instead of thousands of 100-row batches.
 #include <algorithm>
+#include <array>
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -315,6 +316,11 @@ static hipError_t CreateSide2(hipStream_t* s) {
   return hipStreamCreateWithPriority(s, hipStreamNonBlocking, greatest);
 }
 
+// The context's fork / join events and the named finalize / consume events.
+static std::array<hipEvent_t*, 9> NamedEvents(Ctx& c) {
+  return {&c.ev_fork[0], &c.ev_fork[1], &c.ev_join[0], &c.ev_join[1], &c.ev_meta, &c.ev_chain, &c.ev_split, &c.ev_early, &c.ev_pub};
+}
+
 extern "C" int32_t pxg_ctx_create(int32_t device, pxg_ctx** out) {
   if (!out) return SetError(PXG_INVALID_ARGUMENT, "out is null");
   int n = 0;
@@ -333,23 +339,15 @@ extern "C" int32_t pxg_ctx_create(int32_t device, pxg_ctx** out) {
     delete c;
     return SetError(PXG_INTERNAL, "hipStreamCreate: %s", hipGetErrorString(e));
   }
-  if (hipStreamCreateWithFlags(&c->impl.side, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&c->impl.ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->impl.ev_join, hipEventDisableTiming) != hipSuccess ||
-      CreateSide2(&c->impl.side2) != hipSuccess ||
-      hipEventCreateWithFlags(&c->impl.ev_fork2, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->impl.ev_join2, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->impl.ev_meta, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->impl.ev_chain, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->impl.ev_split, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->impl.ev_early, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->impl.ev_pub, hipEventDisableTiming) != hipSuccess) {
+  bool made = hipStreamCreateWithFlags(&c->impl.side[0], hipStreamNonBlocking) == hipSuccess && CreateSide2(&c->impl.side[1]) == hipSuccess;
+  for (hipEvent_t* ev : NamedEvents(c->impl)) made = made && hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess;
+  if (!made) {
     delete c;
     return SetError(PXG_INTERNAL, "side stream / event creation failed");
   }
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->impl.num_cus = prop.multiProcessorCount;
-  if (hipHostMalloc(&c->impl.pinned, Ctx::kPinnedBytes, hipHostMallocDefault) != hipSuccess) {
+  if (hipHostMalloc(reinterpret_cast<void**>(&c->impl.pinned), sizeof(PinnedScratch), hipHostMallocDefault) != hipSuccess) {
     delete c;
     return SetError(PXG_RESOURCE_UNAVAILABLE, "pinned host scratch allocation failed");
   }
@@ -364,19 +362,9 @@ extern "C" int32_t pxg_ctx_destroy(pxg_ctx* ctx) {
   ctx->impl.ResolveTimings();
   for (auto e : ctx->impl.free_events) hipEventDestroy(e);
   if (ctx->impl.pinned) hipHostFree(ctx->impl.pinned);
-  hipStreamSynchronize(ctx->impl.side);
-  hipEventDestroy(ctx->impl.ev_fork);
-  hipEventDestroy(ctx->impl.ev_join);
-  hipStreamDestroy(ctx->impl.side);
-  hipStreamSynchronize(ctx->impl.side2);
-  hipEventDestroy(ctx->impl.ev_fork2);
-  hipEventDestroy(ctx->impl.ev_join2);
-  hipEventDestroy(ctx->impl.ev_meta);
-  hipEventDestroy(ctx->impl.ev_chain);
-  hipEventDestroy(ctx->impl.ev_split);
-  hipEventDestroy(ctx->impl.ev_early);
-  hipEventDestroy(ctx->impl.ev_pub);
-  hipStreamDestroy(ctx->impl.side2);
+  for (hipStream_t side : ctx->impl.side) (void)hipStreamSynchronize(side);
+  for (hipEvent_t* ev : NamedEvents(ctx->impl)) (void)hipEventDestroy(*ev);
+  for (hipStream_t side : ctx->impl.side) (void)hipStreamDestroy(side);
   hipStreamDestroy(ctx->impl.stream);
   delete ctx;
   return PXG_OK;
@@ -781,7 +769,7 @@ int32_t ReadbackSmall(Ctx* ctx, hipStream_t stream, const SmallCopy* items, int 
     c.dst_off[i] = items[i].dst_off;
     c.words[i] = items[i].bytes / 4;
   }
-  return LaunchOn(ctx, stream, "copy_to_host", SmallReadbackKernel, dim3(1), dim3(128), 0, c, static_cast<uint8_t*>(ctx->pinned));
+  return LaunchOn(ctx, stream, "copy_to_host", SmallReadbackKernel, dim3(1), dim3(128), 0, c, reinterpret_cast<uint8_t*>(ctx->pinned));
 }
 
 struct ZeroSpec {

@@ -238,7 +238,7 @@ int32_t ScanExclusiveU64(Ctx* ctx, const uint64_t* in, uint64_t* out, int64_t n,
 // (a datagen append with non-monotone string offsets, 12 groups lost by a sharded C2 run).
 constexpr int64_t kLbMaxTiles = 65536;  // 256M elements; larger scans keep the three-kernel path
 static uint64_t* LbStatus(Ctx* ctx, hipStream_t stream) {
-  const int i = stream == ctx->stream ? 0 : stream == ctx->side ? 1 : stream == ctx->side2 ? 2 : -1;
+  const int i = stream == ctx->stream ? 0 : stream == ctx->side[0] ? 1 : stream == ctx->side[1] ? 2 : -1;
   if (i < 0) return nullptr;
   DevBuf& b = ctx->scan_status[i];
   if (!b.p) {

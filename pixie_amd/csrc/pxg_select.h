@@ -7,6 +7,8 @@
 
 namespace pxg {
 
+struct SelWs;  // pxg_agg_host.h
+
 // One set of big groups for the selection / sort paths: its group and chunk lists (device, with
 // their device counts), host upper bounds for the grids, its chains and selection workspace.
 // Finalize runs two: the designated groups of a fused split (early, from the first pass) and
@@ -14,16 +16,15 @@ namespace pxg {
 struct BigSet {
   BigGroup* big = nullptr;
   BigChunk* chunks = nullptr;
-  const uint32_t* d_count = nullptr;  // groups in the set
-  const uint32_t* d_meta = nullptr;   // [0] chunks, [1] largest group (BigSetupKernel)
-  uint32_t n_big = 0, n_chunks = 0;   // host bounds of both (grids; exact after the meta readback)
-  uint64_t big_max = 0;               // largest group (host; the sort path's merge-pass count)
+  const uint32_t* d_count = nullptr;     // groups in the set
+  const uint32_t* d_meta = nullptr;      // [0] chunks, [1] largest group (BigSetupKernel)
+  const uint32_t* large_cnt = nullptr;   // the groups above kSelLargeN values ...
+  const uint32_t* large_list = nullptr;  // ... and their set indices (BigSetupKernel)
   const uint32_t* chain_starts = nullptr;
   const int32_t* chain_nc = nullptr;
-  DevBuf *spl = nullptr, *cnt = nullptr, *list = nullptr, *bstart = nullptr, *tag = nullptr, *cbase = nullptr, *plan = nullptr,
-         *partial = nullptr;
-  const uint32_t* large_list = nullptr;  // set indices of the groups above kSelLargeN values (BigSetupKernel)
-  const uint32_t* large_cnt = nullptr;
+  SelWs* sel = nullptr;                  // the set's selection workspace
+  uint32_t n_big = 0, n_chunks = 0;      // host bounds of the groups and chunks (grids; exact after the meta readback)
+  uint64_t big_max = 0;                  // largest group (host; the sort path's merge-pass count)
 };
 
 

@@ -778,14 +778,14 @@ __global__ void FallbackListKernel(const BigGroup* __restrict__ groups, const ui
 int32_t SelEnsure(const BigSet& S, uint64_t n, DevBuf& keysA, DevBuf& sel_bin) {
   const size_t nb = S.n_big;
   PXG_RETURN_IF_ERROR(keysA.Ensure(n * 8));
-  PXG_RETURN_IF_ERROR(S.spl->Ensure(nb * kSelBins * 8 + nb * kSelGuideStride * 2 + 16));
-  PXG_RETURN_IF_ERROR(S.cnt->Ensure(nb * kSelBins * 8 + nb * 4 + 16));
-  PXG_RETURN_IF_ERROR(S.list->Ensure(nb * kSelMaxColl * kSelLists * 4 + 16));
-  PXG_RETURN_IF_ERROR(S.bstart->Ensure(nb * (kSelBins + 1) * 4 + 16));
-  PXG_RETURN_IF_ERROR(S.tag->Ensure(nb * kSelBins + 16));
-  PXG_RETURN_IF_ERROR(S.cbase->Ensure(nb * kSelBins * 4 + 16));
-  PXG_RETURN_IF_ERROR(S.plan->Ensure(nb * sizeof(BigPlan) + 16));
-  PXG_RETURN_IF_ERROR(S.partial->Ensure(static_cast<size_t>(S.n_chunks) * kSelMaxRanges * 16 + 16));  // (high, low) words
+  PXG_RETURN_IF_ERROR(S.sel->spl.Ensure(nb * kSelBins * 8 + nb * kSelGuideStride * 2 + 16));
+  PXG_RETURN_IF_ERROR(S.sel->cnt.Ensure(nb * kSelBins * 8 + nb * 4 + 16));
+  PXG_RETURN_IF_ERROR(S.sel->list.Ensure(nb * kSelMaxColl * kSelLists * 4 + 16));
+  PXG_RETURN_IF_ERROR(S.sel->bstart.Ensure(nb * (kSelBins + 1) * 4 + 16));
+  PXG_RETURN_IF_ERROR(S.sel->tag.Ensure(nb * kSelBins + 16));
+  PXG_RETURN_IF_ERROR(S.sel->cbase.Ensure(nb * kSelBins * 4 + 16));
+  PXG_RETURN_IF_ERROR(S.sel->plan.Ensure(nb * sizeof(BigPlan) + 16));
+  PXG_RETURN_IF_ERROR(S.sel->partial.Ensure(static_cast<size_t>(S.n_chunks) * kSelMaxRanges * 16 + 16));  // (high, low) words
   return sel_bin.Ensure(n * 2 + 16);  // per staged value its bin (BigHist -> BigCollect; sets are disjoint)
 }
 
@@ -793,18 +793,18 @@ int32_t SelFront(Ctx* ctx, hipStream_t st, const BigSet& S, const SelIn& in) {
   const uint64_t* vals = in.vals;
   const int at = in.arg_type;
   const uint64_t nb = S.n_big;
-  PXG_HIP(hipMemsetAsync(S.cnt->p, 0, nb * kSelBins * 8 + nb * 4 + 16, st));
-  uint16_t* guide = reinterpret_cast<uint16_t*>(S.spl->as<uint64_t>() + nb * kSelBins);
+  PXG_HIP(hipMemsetAsync(S.sel->cnt.p, 0, nb * kSelBins * 8 + nb * 4 + 16, st));
+  uint16_t* guide = reinterpret_cast<uint16_t*>(S.sel->spl.as<uint64_t>() + nb * kSelBins);
   PXG_RETURN_IF_ERROR(LaunchOn(ctx, st, "quant_sel_sample", BigSampleKernel<kSelSample / 2>, dim3(S.n_big), dim3(kSelSample / 2 / kMsIpt), 0,
-                               static_cast<const BigGroup*>(S.big), S.d_count, vals, at, S.spl->as<uint64_t>(), guide, nullptr, nullptr));
+                               static_cast<const BigGroup*>(S.big), S.d_count, vals, at, S.sel->spl.as<uint64_t>(), guide, nullptr, nullptr));
   const uint32_t n_large = static_cast<uint32_t>(std::min<uint64_t>(S.n_big, in.n / kSelLargeN + 1));  // groups above kSelLargeN: bound
   PXG_RETURN_IF_ERROR(LaunchOn(ctx, st, "quant_sel_sample", BigSampleKernel<kSelSample>, dim3(n_large), dim3(kSelSample / kMsIpt), 0,
-                               static_cast<const BigGroup*>(S.big), S.d_count, vals, at, S.spl->as<uint64_t>(), guide, S.large_list,
+                               static_cast<const BigGroup*>(S.big), S.d_count, vals, at, S.sel->spl.as<uint64_t>(), guide, S.large_list,
                                S.large_cnt));
   const uint32_t cpb = SelChunksPerBlock(S.n_chunks, ctx->num_cus, 3, kSelHistCap);
   return LaunchOn(ctx, st, "quant_sel_hist", at == PXG_FLOAT64 ? BigHistKernel<true> : BigHistKernel<false>, dim3((S.n_chunks + cpb - 1) / cpb),
-                  dim3(256), 0, static_cast<const BigChunk*>(S.chunks), S.d_meta, vals, at, S.spl->as<const uint64_t>(),
-                  static_cast<const uint16_t*>(guide), S.cnt->as<uint32_t>(), S.cnt->as<uint32_t>() + 2 * nb * kSelBins, cpb,
+                  dim3(256), 0, static_cast<const BigChunk*>(S.chunks), S.d_meta, vals, at, S.sel->spl.as<const uint64_t>(),
+                  static_cast<const uint16_t*>(guide), S.sel->cnt.as<uint32_t>(), S.sel->cnt.as<uint32_t>() + 2 * nb * kSelBins, cpb,
                   (*in.sel_bin).as<uint16_t>());
 }
 
@@ -812,41 +812,41 @@ int32_t SelBack(Ctx* ctx, hipStream_t st, const BigSet& S, const SelIn& in) {
   const uint64_t* vals = in.vals;
   const int at = in.arg_type;
   const uint64_t nb = S.n_big;
-  uint32_t* hist = S.cnt->as<uint32_t>();
+  uint32_t* hist = S.sel->cnt.as<uint32_t>();
   uint32_t* cursor = hist + nb * kSelBins;
   uint32_t* nan_cnt = hist + 2 * nb * kSelBins;
   uint32_t* list_cnt = nan_cnt + nb;
   const uint32_t list_cap = static_cast<uint32_t>(nb * kSelMaxColl);
-  uint32_t* lists = S.list->as<uint32_t>();
+  uint32_t* lists = S.sel->list.as<uint32_t>();
   const BigGroup* big = S.big;
   PXG_RETURN_IF_ERROR(LaunchOn(ctx, st, "quant_sel_plan", BigPlanKernel, dim3(S.n_big), dim3(256), 0, big, S.d_count, S.chain_starts,
-                               S.chain_nc, static_cast<const uint32_t*>(hist), static_cast<const uint32_t*>(nan_cnt), S.bstart->as<uint32_t>(),
-                               S.tag->as<uint8_t>(), S.cbase->as<uint32_t>(), S.plan->as<BigPlan>(), in.d_fallback, lists, list_cap, list_cnt));
+                               S.chain_nc, static_cast<const uint32_t*>(hist), static_cast<const uint32_t*>(nan_cnt), S.sel->bstart.as<uint32_t>(),
+                               S.sel->tag.as<uint8_t>(), S.sel->cbase.as<uint32_t>(), S.sel->plan.as<BigPlan>(), in.d_fallback, lists, list_cap, list_cnt));
   const uint32_t cpb = SelChunksPerBlock(S.n_chunks, ctx->num_cus, 3, 64);  // 3 resident per CU (LDS)
   PXG_RETURN_IF_ERROR(LaunchOn(ctx, st, "quant_sel_collect", at == PXG_FLOAT64 ? BigCollectKernel<true> : BigCollectKernel<false>,
                                dim3((S.n_chunks + cpb - 1) / cpb), dim3(256), 0, static_cast<const BigChunk*>(S.chunks), S.d_meta,
-                               S.plan->as<const BigPlan>(), vals, at, (*in.sel_bin).as<const uint16_t>(), S.tag->as<const uint8_t>(),
-                               S.cbase->as<const uint32_t>(), cursor, (*in.keysA).as<uint64_t>(), S.partial->as<double>(), cpb));
+                               S.sel->plan.as<const BigPlan>(), vals, at, (*in.sel_bin).as<const uint16_t>(), S.sel->tag.as<const uint8_t>(),
+                               S.sel->cbase.as<const uint32_t>(), cursor, (*in.keysA).as<uint64_t>(), S.sel->partial.as<double>(), cpb));
   PXG_RETURN_IF_ERROR(LaunchOn(ctx, st, "quant_sel_bin_sort", BigBinSortKernel,
                                dim3(std::min<uint32_t>(list_cap / 4 + 1, static_cast<uint32_t>(ctx->num_cus) * 4)), dim3(256), 0, big,
                                static_cast<const uint32_t*>(lists), static_cast<const uint32_t*>(list_cnt), static_cast<const uint32_t*>(hist),
-                               S.cbase->as<const uint32_t>(), (*in.keysA).as<uint64_t>()));
+                               S.sel->cbase.as<const uint32_t>(), (*in.keysA).as<uint64_t>()));
   PXG_RETURN_IF_ERROR(LaunchOn(ctx, st, "quant_sel_bin_sort", BigBinSortLargeKernel,
                                dim3(std::min<uint32_t>(list_cap, static_cast<uint32_t>(ctx->num_cus))), dim3(256), 0, big,
                                static_cast<const uint32_t*>(lists + list_cap), static_cast<const uint32_t*>(list_cnt + 1),
-                               static_cast<const uint32_t*>(hist), S.cbase->as<const uint32_t>(), (*in.keysA).as<uint64_t>()));
+                               static_cast<const uint32_t*>(hist), S.sel->cbase.as<const uint32_t>(), (*in.keysA).as<uint64_t>()));
   PXG_RETURN_IF_ERROR(LaunchOn(ctx, st, "quant_sel_bin_sort", BigBinSortHugeKernel,
                                dim3(std::min<uint32_t>(list_cap, static_cast<uint32_t>(ctx->num_cus))), dim3(kSelHugeThreads), 0, big,
                                static_cast<const uint32_t*>(lists + 2 * list_cap), static_cast<const uint32_t*>(list_cnt + 2),
-                               static_cast<const uint32_t*>(hist), S.cbase->as<const uint32_t>(), (*in.keysA).as<uint64_t>()));
-  return LaunchOn(ctx, st, "quant_sel_digest", BigSelDigestKernel, dim3(S.n_big), dim3(256), 0, big, S.d_count, S.plan->as<const BigPlan>(),
-                  S.chain_starts, S.bstart->as<const uint32_t>(), S.cbase->as<const uint32_t>(), (*in.keysA).as<const uint64_t>(),
-                  S.partial->as<const double>(), in.out);
+                               static_cast<const uint32_t*>(hist), S.sel->cbase.as<const uint32_t>(), (*in.keysA).as<uint64_t>()));
+  return LaunchOn(ctx, st, "quant_sel_digest", BigSelDigestKernel, dim3(S.n_big), dim3(256), 0, big, S.d_count, S.sel->plan.as<const BigPlan>(),
+                  S.chain_starts, S.sel->bstart.as<const uint32_t>(), S.sel->cbase.as<const uint32_t>(), (*in.keysA).as<const uint64_t>(),
+                  S.sel->partial.as<const double>(), in.out);
 }
 
 int32_t SelFallbackList(Ctx* ctx, const BigSet& S, uint32_t* list, uint32_t* count) {
   return Launch(ctx, "quant_fallback_list", FallbackListKernel, dim3((S.n_big + 255) / 256), dim3(256), 0, static_cast<const BigGroup*>(S.big),
-                S.d_count, S.plan->as<const BigPlan>(), list, count);
+                S.d_count, S.sel->plan.as<const BigPlan>(), list, count);
 }
 
 }  // namespace pxg

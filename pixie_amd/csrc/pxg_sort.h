@@ -63,8 +63,8 @@ int32_t DesignateLargeGroups(Ctx* ctx, const unsigned long long* slots, uint32_t
                              uint64_t** d_ftotal);
 // Step 2: the 9-bit first pass.  Designated records' values go straight to their final place in
 // vfin; rest records (key = rest id, values) to kout_rest / vrest at [0, n_rest), sorted by their
-// low digit.  Enqueues n_rest (u32 at pinned + 104) and *d_ftotal (u64 at pinned + 112) to
-// pinned memory and records ctx->ev_split before the scatter; *base_out: the bucket bases.
+// low digit.  Enqueues n_rest and *d_ftotal to the pinned scratch
+// (PinnedScratch::split_n_rest / split_ftotal) and records ctx->ev_split before the scatter; *base_out: the bucket bases.
 int32_t FusedSplitPass(Ctx* ctx, const uint32_t* st_slot, uint64_t n, const uint32_t* rank, uint32_t cap, uint32_t G, const uint64_t* d_ftotal,
                        ConstValPtrs vin, int nvs, DevBuf& split_hist, DevBuf& split_tot, DevBuf& fs_keys, RadixPassWs& rs, uint32_t* kout_rest,
                        ValPtrs vrest, ValPtrs vfin, const uint32_t** base_out);

@@ -263,6 +263,17 @@ def test_selection_path_int64_values_match_sort_path(ctx):
                 assert abs(a - b) <= 1e-12 * max(abs(a), abs(b)), (k, name, a, b)
 
 
+def _groups_beyond_one_digit(fallback):
+    """_groups plus 400 small groups: more than 256 groups, so a forced fused split runs."""
+    keys, vals, sizes = _groups(fallback)
+    rng = np.random.default_rng(77)
+    small = {f"s{i}": rng.lognormal(1, 1, 100) for i in range(400)}
+    keys = keys + [k for k, v in small.items() for _ in v]
+    vals = np.concatenate([vals] + list(small.values()))
+    sizes.update({k: len(v) for k, v in small.items()})
+    return keys, vals, sizes
+
+
 @pytest.mark.parametrize("fallback", [None, "nan"])
 def test_early_set_matches_late_set(ctx, monkeypatch, fallback):
     """Fused split (forced on, > 256 groups): the designated big groups take the selection path
@@ -270,12 +281,7 @@ def test_early_set_matches_late_set(ctx, monkeypatch, fallback):
     class 3 of the classification).  Same values, same kernels: the same quantiles (big groups to
     the last bits of their inside-bin sums), and a fallback group in either set goes to the sort
     path on its own (identical)."""
-    keys, vals, sizes = _groups(fallback)
-    rng = np.random.default_rng(77)
-    small = {f"s{i}": rng.lognormal(1, 1, 100) for i in range(400)}
-    keys = keys + [k for k, v in small.items() for _ in v]
-    vals = np.concatenate([vals] + list(small.values()))
-    sizes.update({k: len(v) for k, v in small.items()})
+    keys, vals, sizes = _groups_beyond_one_digit(fallback)
     monkeypatch.setenv("PXG_FSPLIT", "1")
     monkeypatch.setenv("PXG_EARLY_BIG", "0")
     late, info_l = _run_info(ctx, keys, vals, force_sort=False)
@@ -293,6 +299,64 @@ def test_early_set_matches_late_set(ctx, monkeypatch, fallback):
                 assert a == b or (a != a and b != b), (k, name, a, b)
             else:  # (inside-bin sums: atomics, last bits run to run, as in the late set alone)
                 assert abs(a - b) <= 1e-12 * max(abs(a), abs(b)), (k, name, a, b)
+
+
+@pytest.mark.parametrize("fallback", [None, "nan"])
+def test_early_result_lanes_with_fused_split_early_set_and_fallback(ctx, monkeypatch, fallback):
+    """Early results x fused split x early set x fallback: pxg_agg_finalize_result with the
+    quantiles column asked for as lanes issues the key / count copies and the lanes inside the
+    finalize; on the same handle (the same finalized state, so the same group order)
+    pxg_agg_quantile_lanes and pxg_agg_result_skip give identical lanes, finiteness bytes, key
+    and count columns.  With the NaN group the sort path recomputes it after the final read-back,
+    and the lanes issued a second time must have rewritten the early host blocks."""
+    from device_runner import _upload
+    from pixie_amd.pipeline import LinearQuery
+    keys, vals, sizes = _groups_beyond_one_digit(fallback)
+    monkeypatch.setenv("PXG_FSPLIT", "1")
+    monkeypatch.delenv("PXG_EARLY_BIG", raising=False)
+    monkeypatch.delenv("PXG_BIG_SORT", raising=False)
+    plan = P.linear_plan([P.source_op("t", [5, 4], ["k", "v"], [0, 1]),
+                          P.agg_op([0], [P.agg_expr("quantiles", [P.col(1)], [4]), P.agg_expr("count", [P.col(1)], [4], fid=1)]),
+                          P.sink_op("out")])
+    a = LinearQuery(plan, [5, 4]).make_agg(ctx)
+    t = _upload(ctx, [5, 4], [[Column.from_values(5, keys), Column(4, values=vals)]])
+    lib = ctx.lib
+    mask = 0b1001000  # p50, p99
+    skip = (C.c_uint8 * 3)(0, 0x80 | mask, 0)
+
+    def arr(ptr, ctype, n):
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,)).copy()
+
+    def columns(outs, G):  # (key offsets, key payload, lanes, finiteness bytes, counts) as arrays
+        offs = arr(outs[0].offsets, C.c_int32, G + 1)
+        assert outs[0].data_len == offs[-1] and outs[1].data_len == G
+        return (offs, arr(outs[0].data, C.c_uint8, int(offs[-1])), arr(outs[1].values, C.c_double, 2 * G),
+                arr(outs[1].data, C.c_uint8, G), arr(outs[2].values, C.c_int64, G))
+
+    a.consume(t)
+    ng = C.c_int64(0)
+    early = (_lib.ColumnOut * 3)()
+    assert lib.pxg_agg_finalize_result(a.h, C.byref(ng), early, 3, skip) == 0
+    G = ng.value
+    assert G == len(sizes) > 256
+    info = a.info()
+    got = columns(early, G)
+    lib.pxg_result_free(early, 3)
+    lanes = np.zeros(2 * G, dtype=np.float64)
+    fin = np.zeros(G, dtype=np.uint8)
+    assert lib.pxg_agg_quantile_lanes(a.h, 0, mask, lanes.ctypes.data_as(C.c_void_p), fin.ctypes.data_as(C.c_void_p)) == 0
+    late = (_lib.ColumnOut * 3)()
+    assert lib.pxg_agg_result_skip(a.h, late, 3, skip) == 0
+    want = columns(late, G)
+    lib.pxg_result_free(late, 3)
+    a.close()
+    t.close()
+    assert np.array_equal(got[2], lanes) and np.array_equal(got[3], fin)
+    for g, w in zip(got, want):
+        assert g.tobytes() == w.tobytes()
+    assert sorted(got[4]) == sorted(sizes.values())
+    if fallback:
+        assert info["big_sort_groups"] >= 1, info
 
 
 def test_two_quantile_udas_with_a_fallback_group_sort_every_big_group(ctx):
